@@ -26,10 +26,6 @@ import sys
 import threading
 import time
 
-# More hardware queues than ROCm's default of 4 per priority level, before the HIP runtime starts: with a process group the process
-# holds RCCL's streams beside the towers', and streams that share a queue serialize.  The towers' side streams are
-# also high-priority (their own queue pool), so this is the second line of defence.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: RCCL's peer mappings need it on this driver (also under torchrun)
 
 import torch
@@ -71,7 +67,29 @@ def parse():
     ap.add_argument("--eval", action="store_true", help="eval path (SURVEY §8f-2, not the headline metric): no-grad embedding forward + K10 top-k search")
     ap.add_argument("--eval-queries", type=int, default=1024, help="--eval: queries per top-k launch")
     ap.add_argument("--eval-keys", type=int, default=409600, help="--eval: size of the key bank (BIOSCAN-5M-sized by default; 21000 = BIOSCAN-1M)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all): training = "
+                         "loss, params, grads; --eval = the embeddings.  Inputs are seeded, so two builds can be compared output for output")
     return ap.parse_args()
+
+
+DUMP_MAX_ELEMS = 4 << 20   # per dumped array (16 MB of fp32): at most three such arrays plus the loss stay under 64 MB
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """`--dump-outputs DIR`: each array as DIR/<name>.npy, float64 if it is float64 on the device, float32 otherwise.  One with more than
+    DUMP_MAX_ELEMS elements is written as a fixed, seeded sample of its flattened elements (the positions depend on its length only)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.numpy())
 
 
 class GemmTimer:
@@ -409,6 +427,8 @@ def eval_bench(args, model, batch, b, world, rank, dev, dist, timer):
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {f"{n}_embeddings": t for n, t in zip(("image", "dna", "text"), out[:3]) if t is not None})
     gemm = None
     if not args.no_gemm_timing:
         model.overlap_towers = False            # per-launch durations of the kernel itself (towers serialized), as in the training line
@@ -860,6 +880,9 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's loss, the trainable parameters it left and its gradients (flat-bucket order), before any later pass moves them
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "params": trainer.optimizer.flat_p, "grads": trainer.optimizer.flat_g})
 
     # Kernel passes for `roofline` (same step, right after the timed region, not part of `value`): HIP events around every
     # GEMM launch, recorded on the launch stream.  Pass 1 runs exactly like the timed region: the two towers overlap on
