@@ -122,6 +122,22 @@ SIGNATURES = {
     "clibd_batch_sum_f32": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p]),
     "clibd_bert_embed_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "clibd_slice_rows_cast_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    # deterministic mode (partials workspaces + fixed-order sums)
+    "clibd_layernorm_bwd_pg_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_layernorm_bwd_pg_ordered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               C.c_uint32, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_layernorm_param_grads_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_layernorm_param_grads_ordered": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, C.c_uint32, c_int, c_float,
+                                                    c_void_p, c_size_t, c_void_p]),
+    "clibd_batch_sum_workspace_bytes": (c_size_t, [c_int, c_size_t]),
+    "clibd_batch_sum_f32_ordered": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_bert_embed_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "clibd_bert_embed_bwd_ordered": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_colsum_bf16_ordered": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_gemm_tn_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_gemm_bf16_tn_splitk_ordered": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                                  c_void_p, c_size_t, c_void_p]),
     "clibd_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
 }
 

@@ -116,6 +116,8 @@ def save_training_state(path: str, model: torch.nn.Module, optimizer=None, sched
     state = {"model": model.state_dict(), "epoch": epoch}
     if hasattr(model, "numerics"):
         state["numerics"] = model.numerics()   # which arithmetic produced these weights (engine.NUMERICS_CHOICES + fp8-forward flag)
+    if hasattr(model, "deterministic"):
+        state["deterministic"] = bool(model.deterministic())   # fixed-order reductions (SimpleCLIP.set_deterministic)
     if optimizer is not None and hasattr(optimizer, "exp_avg"):
         state["optimizer"] = {"exp_avg": optimizer.exp_avg.detach().cpu(), "exp_avg_sq": optimizer.exp_avg_sq.detach().cpu(),
                               "step_count": optimizer.step_count, "layout": _optimizer_layout(model, optimizer),

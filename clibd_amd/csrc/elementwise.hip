@@ -286,21 +286,27 @@ __global__ __launch_bounds__(256) void token_mean_bwd_kernel(const float* __rest
     }
 }
 
-// column sums of bf16 [M,N] into fp32 out[N] (atomic accumulate): block = 256 rows chunk x 64 columns
+// column sums of bf16 [M,N] into fp32 out[N] (atomic accumulate): block = 256 rows chunk x 64 columns.  ws != nullptr (deterministic
+// mode): block row y walks the chunks y, y + gridDim.y, ... and stores its partial to ws[y * N + c] (summed in order by ordered_colsum_kernel)
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const unsigned short* __restrict__ x, int ld, int M, int N,
-                                                          float* __restrict__ out) {
+                                                          float* __restrict__ out, float* __restrict__ ws) {
     __shared__ float part[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + lane;
-    const int r0 = blockIdx.y * 256;
     float s = 0.f;
     if (c < N) {
-        const int r1 = min(r0 + 256, M);
-        for (int r = r0 + wave; r < r1; r += 4) s += bf2f(x[(size_t)r * ld + c]);
+        for (int r0 = blockIdx.y * 256; r0 < M; r0 += gridDim.y * 256) {
+            const int r1 = min(r0 + 256, M);
+            for (int r = r0 + wave; r < r1; r += 4) s += bf2f(x[(size_t)r * ld + c]);
+        }
     }
     part[wave][lane] = s;
     __syncthreads();
-    if (wave == 0 && c < N) atomicAdd(out + c, part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane]);
+    if (wave == 0 && c < N) {
+        const float t = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
+        if (ws != nullptr) ws[(size_t)blockIdx.y * N + c] = t;
+        else atomicAdd(out + c, t);
+    }
 }
 
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ x, int B, int S, int H,
@@ -588,8 +594,26 @@ extern "C" int clibd_token_mean_bwd(const float* dout, int B, int S, int H, floa
 extern "C" int clibd_colsum_bf16(const void* x, int ld, int M, int N, float* out, void* stream) {
     if (!x || !out || M <= 0 || N <= 0 || ld < N) return set_error(CLIBD_EINVAL, "colsum: bad args");
     dim3 grid((N + 63) / 64, (M + 255) / 256);
-    hipLaunchKernelGGL(colsum_bf16_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ld, M, N, out);
+    hipLaunchKernelGGL(colsum_bf16_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ld, M, N, out, (float*)nullptr);
     return check_launch("colsum_bf16");
+}
+
+// deterministic mode: at most COLSUM_ORDERED_ROWS partial rows (chunk-strided), then ordered_colsum_kernel
+constexpr int COLSUM_ORDERED_ROWS = 256;
+extern "C" size_t clibd_colsum_workspace_bytes(int M, int N) {
+    if (M <= 0 || N <= 0) return 0;
+    return (size_t)min((M + 255) / 256, COLSUM_ORDERED_ROWS) * (size_t)N * sizeof(float);
+}
+
+extern "C" int clibd_colsum_bf16_ordered(const void* x, int ld, int M, int N, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !out || !workspace || M <= 0 || N <= 0 || ld < N) return set_error(CLIBD_EINVAL, "colsum_ordered: bad args");
+    if (!aligned16(workspace) || workspace_bytes < clibd_colsum_workspace_bytes(M, N))
+        return set_error(CLIBD_EINVAL, "colsum_ordered: workspace too small or misaligned (clibd_colsum_workspace_bytes)");
+    const int rows = min((M + 255) / 256, COLSUM_ORDERED_ROWS);
+    hipLaunchKernelGGL(colsum_bf16_kernel, dim3((N + 63) / 64, rows), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ld, M, N, out,
+                       (float*)workspace);
+    if (int e = check_launch("colsum_bf16_ordered")) return e;
+    return ordered_colsum_launch((const float*)workspace, rows, N, out, N, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int clibd_gather_rows(const float* x, int B, int S, int H, float* out, void* stream) {

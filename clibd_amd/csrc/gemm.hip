@@ -247,6 +247,46 @@ __global__ __launch_bounds__(256) void colsum_partials_kernel(const float* __res
     colsum[c] += (s0 + s1) + (s2 + s3);
 }
 
+// out[c] += sum_b partials[b, c] for the partials-workspace forms of the training path's reductions (LayerNorm / embedding / bias
+// gradients; the deterministic mode): block = 64 columns x G row groups (one wave each, G = min(16, nblk)); group w sums rows
+// [w * per, (w + 1) * per) in row order (eight loads in flight ahead of the adds), the G group sums are combined in group order.
+// The order depends on (nblk, C) only, never on timing: the result repeats bit for bit.
+__global__ __launch_bounds__(1024) void ordered_colsum_kernel(const float* __restrict__ partials, int nblk, int C, float* __restrict__ out, int split,
+                                                              float* __restrict__ out_b) {
+    __shared__ float part[16][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, G = blockDim.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    const int per = (nblk + G - 1) / G;
+    const int b1 = min((w + 1) * per, nblk);
+    float s = 0.f;
+    if (c < C) {
+        int b = w * per;
+        for (; b + 8 <= b1; b += 8) {
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = partials[(size_t)(b + k) * C + c];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s += v[k];
+        }
+        for (; b < b1; ++b) s += partials[(size_t)b * C + c];
+    }
+    part[w][lane] = s;
+    __syncthreads();
+    if (w == 0 && c < C) {
+        float t = part[0][lane];
+        for (int k = 1; k < G; ++k) t += part[k][lane];
+        if (c < split) out[c] += t;
+        else out_b[c - split] += t;
+    }
+}
+
+int ordered_colsum_launch(const float* partials, int nblk, int C, float* out, int split, float* out_b, hipStream_t stream) {
+    if (nblk <= 0 || C <= 0) return CLIBD_OK;
+    const int G = nblk < 16 ? nblk : 16;
+    hipLaunchKernelGGL(ordered_colsum_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64 * G), 0, stream, partials, nblk, C, out, split, out_b);
+    return check_launch("ordered_colsum");
+}
+
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* in, unsigned short* out, size_t n) {
     size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const size_t stride = (size_t)gridDim.x * blockDim.x * 4;
@@ -497,6 +537,36 @@ extern "C" int clibd_gemm_bf16_tn_splitk(const void* A, int lda, const void* B, 
     hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, splits, n4,
                        out_f32, accumulate);
     return check_launch("reduce_splits");
+}
+
+// deterministic mode: the TN split-K weight gradient whose bias gradient (colsum_a) is stored as one partial per M-slice (at most
+// M / 256 slices: plan_k_slices keeps every slice >= 4 K-tiles) and summed in slice order, after the slices' reduce_splits_kernel
+extern "C" size_t clibd_gemm_tn_colsum_workspace_bytes(int M, int Na) {
+    if (M <= 0 || Na <= 0) return 0;
+    const int slots = M / 256 > 1 ? M / 256 : 1;
+    return (size_t)slots * (size_t)Na * sizeof(float);
+}
+
+extern "C" int clibd_gemm_bf16_tn_splitk_ordered(const void* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* out_f32, int ld_out,
+                                                 int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
+                                                 size_t colsum_workspace_bytes, void* stream) {
+    if (!A || !B || !out_f32 || !workspace || !colsum_a || !colsum_workspace) return set_error(CLIBD_EINVAL, "gemm_tn_splitk_ordered: null pointer");
+    if (M <= 0 || Na <= 0 || Nb <= 0 || lda < Na || ldb < Nb || ld_out != Nb) return set_error(CLIBD_EINVAL, "gemm_tn_splitk_ordered: bad shape (out must be dense [Na,Nb])");
+    if ((lda & 7) || (ldb & 7) || !aligned16(A) || !aligned16(B) || !aligned16(out_f32) || !aligned16(workspace) || !aligned16(colsum_workspace))
+        return set_error(CLIBD_EINVAL, "gemm_tn_splitk_ordered: alignment");
+    if (colsum_workspace_bytes < clibd_gemm_tn_colsum_workspace_bytes(M, Na))
+        return set_error(CLIBD_EINVAL, "gemm_tn_splitk_ordered: colsum workspace too small (clibd_gemm_tn_colsum_workspace_bytes)");
+    const int splits = gemm256_tn_splitk_launch((const unsigned short*)A, lda, (const unsigned short*)B, ldb, M, Na, Nb, (float*)workspace,
+                                                workspace_bytes / sizeof(float), colsum_a, (hipStream_t)stream, (float*)colsum_workspace);
+    if (splits <= 0) return set_error(CLIBD_EINVAL, "gemm_tn_splitk_ordered: shape not supported (need M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, workspace)");
+    if (int e = check_launch("gemm256_tn")) return e;
+    const size_t n4 = (size_t)Na * Nb / 4;
+    size_t blocks = (n4 + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, splits, n4,
+                       out_f32, accumulate);
+    if (int e = check_launch("reduce_splits")) return e;
+    return ordered_colsum_launch((const float*)colsum_workspace, splits, Na, colsum_a, Na, nullptr, (hipStream_t)stream);
 }
 
 static inline int transpose_row_tile(int ld_out) { return ld_out >= 1024 ? 256 : 64; }

@@ -47,6 +47,7 @@ struct TnParams {
     float* partials;           // [splits][Na][Nb]
     long long split_stride;    // Na * Nb
     float* colsum;             // optional [Na]: += column sums of A (the bias gradient rides along, see CS below)
+    float* colsum_partials;    // deterministic mode: [splits][Na], the slice sums stored instead of added atomically (nullptr: atomics)
 };
 
 typedef int i32x2 __attribute__((ext_vector_type(2)));
@@ -266,7 +267,11 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
 #pragma unroll
                         for (int n = 0; n < 2; ++n)
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) atomicAdd(p.colsum + row0 + 128 * hn + 16 * n + r, csum[hn][n][r]);
+                            for (int r = 0; r < 4; ++r) {
+                                const int row = row0 + 128 * hn + 16 * n + r;
+                                if (p.colsum_partials != nullptr) p.colsum_partials[(size_t)split_issue * p.Na + row] = csum[hn][n][r];
+                                else atomicAdd(p.colsum + row, csum[hn][n][r]);
+                            }
                 }
             }
         }
@@ -276,7 +281,7 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
 
 // Returns the number of M-slices used (>= 1) or 0 when the shape is not one this kernel takes.
 int gemm256_tn_splitk_launch(const unsigned short* A, int lda, const unsigned short* B, int ldb, int M, int Na, int Nb, float* partials,
-                             size_t partials_elems, float* colsum, hipStream_t stream) {
+                             size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials) {
     if (M <= 0 || M % 128 != 0 || Na % 256 != 0 || Nb % 256 != 0 || Na <= 0 || Nb <= 0) return 0;
     const int nk = M / 64;
     if (nk < 4) return 0;
@@ -301,6 +306,7 @@ int gemm256_tn_splitk_launch(const unsigned short* A, int lda, const unsigned sh
     q.partials = partials;
     q.split_stride = (long long)Na * Nb;
     q.colsum = colsum;
+    q.colsum_partials = colsum != nullptr ? colsum_partials : nullptr;
     static const bool attr_ok = hipFuncSetAttribute((const void*)gemm256_tn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS) == hipSuccess &&
                                 hipFuncSetAttribute((const void*)gemm256_tn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS) == hipSuccess;
     if (!attr_ok) return 0;

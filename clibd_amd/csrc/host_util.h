@@ -34,4 +34,8 @@ inline unsigned grid_for(size_t n, int per_block = 256, unsigned cap = 4096) {
     return b < 1 ? 1u : (unsigned)b;
 }
 
+// out[c] += sum_b partials[b * C + c] (c < split; out_b[c - split] for the rest) in an order that depends on (nblk, C) only:
+// the fixed-order second kernel of every partials-workspace form (gemm.hip).  Returns check_launch's code.
+int ordered_colsum_launch(const float* partials, int nblk, int C, float* out, int split, float* out_b, hipStream_t stream);
+
 }  // namespace clibd

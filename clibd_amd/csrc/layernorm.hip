@@ -180,7 +180,7 @@ __device__ __forceinline__ void layernorm_bwd_body(const unsigned short* __restr
                                                    int drop_thr16, float drop_scale, float* __restrict__ dgamma,
                                                    float* __restrict__ dbeta, const unsigned short* __restrict__ dres_b16,
                                                    unsigned short* __restrict__ dx_res_b16, unsigned char* __restrict__ dx_fp8,
-                                                   float* __restrict__ row_dequant) {
+                                                   float* __restrict__ row_dequant, float* __restrict__ pg_ws) {
     const int lane = threadIdx.x & 63;
     const int wave_in_grid = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * 4;
@@ -338,9 +338,18 @@ __device__ __forceinline__ void layernorm_bwd_body(const unsigned short* __restr
             *(f32x4*)(&pg_lds[1][wv][c]) = pbet[j];
         }
         __syncthreads();
+        // pg_ws (deterministic mode): block b stores its [2, H] partial as workspace row b, summed in block order by ordered_colsum_kernel
+        float* wrow = pg_ws != nullptr ? pg_ws + (size_t)blockIdx.x * 2 * H : nullptr;
         for (int c = threadIdx.x; c < H; c += 256) {
-            atomicAdd(dgamma + c, (pg_lds[0][0][c] + pg_lds[0][1][c]) + (pg_lds[0][2][c] + pg_lds[0][3][c]));
-            atomicAdd(dbeta + c, (pg_lds[1][0][c] + pg_lds[1][1][c]) + (pg_lds[1][2][c] + pg_lds[1][3][c]));
+            const float sg = (pg_lds[0][0][c] + pg_lds[0][1][c]) + (pg_lds[0][2][c] + pg_lds[0][3][c]);
+            const float sb = (pg_lds[1][0][c] + pg_lds[1][1][c]) + (pg_lds[1][2][c] + pg_lds[1][3][c]);
+            if (wrow != nullptr) {
+                wrow[c] = sg;
+                wrow[H + c] = sb;
+            } else {
+                atomicAdd(dgamma + c, sg);
+                atomicAdd(dbeta + c, sb);
+            }
         }
     }
 }
@@ -352,9 +361,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short
                                                             float* __restrict__ dx_f32, unsigned short* __restrict__ dx_bf16, unsigned drop_seed,
                                                             int drop_thr16, float drop_scale, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta, const unsigned short* __restrict__ dres_b16,
-                                                            unsigned short* __restrict__ dx_res_b16) {
+                                                            unsigned short* __restrict__ dx_res_b16, float* __restrict__ pg_ws) {
     layernorm_bwd_body<NCH, PG, ROWS, false>(dy_bf16, dy_f32, x, stats, gamma, M, H, dres, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, dgamma,
-                                             dbeta, dres_b16, dx_res_b16, nullptr, nullptr);
+                                             dbeta, dres_b16, dx_res_b16, nullptr, nullptr, pg_ws);
 }
 // (four waves per SIMD, as the plain kernel reaches at H = 768: without the bound the two-row form takes 131 registers — three waves)
 #ifndef CLIBD_LNB8_WAVES
@@ -369,7 +378,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLIBD_LNB8_
                                                                 unsigned short* __restrict__ dx_res_b16, unsigned char* __restrict__ dx_fp8,
                                                                 float* __restrict__ row_dequant) {
     layernorm_bwd_body<NCH, false, ROWS, true>(dy_bf16, dy_f32, x, stats, gamma, M, H, dres, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, nullptr,
-                                               nullptr, dres_b16, dx_res_b16, dx_fp8, row_dequant);
+                                               nullptr, dres_b16, dx_res_b16, dx_fp8, row_dequant, nullptr);
 }
 
 // 8-bit dgrad with TRAINABLE base weights (round 6, full fine-tune): the e4m3 rows for the dgrad, the bf16 copy for the weight gradient and
@@ -381,9 +390,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_fp8_pg_kernel(const unsigne
                                                                    float* __restrict__ dx_f32, unsigned short* __restrict__ dx_bf16, unsigned drop_seed,
                                                                    int drop_thr16, float drop_scale, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                                    const unsigned short* __restrict__ dres_b16, unsigned short* __restrict__ dx_res_b16,
-                                                                   unsigned char* __restrict__ dx_fp8, float* __restrict__ row_dequant) {
+                                                                   unsigned char* __restrict__ dx_fp8, float* __restrict__ row_dequant,
+                                                                   float* __restrict__ pg_ws) {
     layernorm_bwd_body<NCH, true, 1, true>(dy_bf16, dy_f32, x, stats, gamma, M, H, dres, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, dgamma,
-                                           dbeta, dres_b16, dx_res_b16, dx_fp8, row_dequant);
+                                           dbeta, dres_b16, dx_res_b16, dx_fp8, row_dequant, pg_ws);
 }
 
 static inline int ln_grid(int M) {
@@ -459,7 +469,8 @@ extern "C" int clibd_layernorm_fwd_fp8(const float* x, int M, int H, const float
 static int layernorm_bwd_impl(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats,
                               const float* gamma, int M, int H, const float* dres_f32, float* dx_f32,
                               void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, float* dgamma, float* dbeta, void* stream,
-                              const void* dres_b16 = nullptr, void* dx_res_b16 = nullptr, void* dx_fp8 = nullptr, float* row_dequant = nullptr) {
+                              const void* dres_b16 = nullptr, void* dx_res_b16 = nullptr, void* dx_fp8 = nullptr, float* row_dequant = nullptr,
+                              float* pg_ws = nullptr) {
     if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "layernorm_bwd: bad dropout threshold");
     if (!x || !stats || !gamma) return set_error(CLIBD_EINVAL, "layernorm_bwd: null pointer");
     if ((dy_bf16 == nullptr) == (dy_f32 == nullptr)) return set_error(CLIBD_EINVAL, "layernorm_bwd: exactly one of dy_bf16/dy_f32");
@@ -487,7 +498,7 @@ static int layernorm_bwd_impl(const void* dy_bf16, const float* dy_f32, const fl
         if (dx_fp8 && pg)                                                                                      \
             hipLaunchKernelGGL((layernorm_bwd_fp8_pg_kernel<N>), grid, block, 0, st, (const unsigned short*)dy_bf16, dy_f32, x, \
                                stats, gamma, M, H, dres_f32, dx_f32, (unsigned short*)dx_bf16, drop_seed, drop_thr16, drop_scale, dgamma, dbeta, \
-                               (const unsigned short*)dres_b16, (unsigned short*)dx_res_b16, (unsigned char*)dx_fp8, row_dequant); \
+                               (const unsigned short*)dres_b16, (unsigned short*)dx_res_b16, (unsigned char*)dx_fp8, row_dequant, pg_ws); \
         else if (dx_fp8)                                                                                       \
             hipLaunchKernelGGL((layernorm_bwd_fp8_kernel<N, (N <= 3 ? R : 1)>), grid, block, 0, st, (const unsigned short*)dy_bf16, dy_f32, x, /* (two rows only up to H = 768: see two_rows) */ \
                                stats, gamma, M, H, dres_f32, dx_f32, (unsigned short*)dx_bf16, drop_seed, drop_thr16, drop_scale, \
@@ -495,11 +506,11 @@ static int layernorm_bwd_impl(const void* dy_bf16, const float* dy_f32, const fl
         else if (pg)                                                                                            \
             hipLaunchKernelGGL((layernorm_bwd_kernel<N, true, 1>), grid, block, 0, st, (const unsigned short*)dy_bf16, dy_f32, x, \
                                stats, gamma, M, H, dres_f32, dx_f32, (unsigned short*)dx_bf16, drop_seed, drop_thr16, drop_scale, dgamma, dbeta, \
-                               (const unsigned short*)dres_b16, (unsigned short*)dx_res_b16);                  \
+                               (const unsigned short*)dres_b16, (unsigned short*)dx_res_b16, pg_ws);           \
         else                                                                                                   \
             hipLaunchKernelGGL((layernorm_bwd_kernel<N, false, R>), grid, block, 0, st, (const unsigned short*)dy_bf16, dy_f32, x, \
                                stats, gamma, M, H, dres_f32, dx_f32, (unsigned short*)dx_bf16, drop_seed, drop_thr16, drop_scale, \
-                               (float*)nullptr, (float*)nullptr, (const unsigned short*)dres_b16, (unsigned short*)dx_res_b16); \
+                               (float*)nullptr, (float*)nullptr, (const unsigned short*)dres_b16, (unsigned short*)dx_res_b16, (float*)nullptr); \
     } while (0)
 #define LAUNCH(N)                    \
     do {                             \
@@ -514,7 +525,8 @@ static int layernorm_bwd_impl(const void* dy_bf16, const float* dy_f32, const fl
     }
 #undef LAUNCH
 #undef LAUNCH_R
-    return check_launch("layernorm_bwd");
+    if (int e = check_launch("layernorm_bwd")) return e;
+    return pg_ws != nullptr ? ordered_colsum_launch(pg_ws, (int)grid.x, 2 * H, dgamma, H, dbeta, st) : CLIBD_OK;
 }
 
 extern "C" int clibd_layernorm_bwd_drop(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats,
@@ -570,4 +582,24 @@ extern "C" int clibd_layernorm_bwd_any(const void* dy_bf16, const float* dy_f32,
                                        void* stream) {
     return layernorm_bwd_impl(dy_bf16, dy_f32, x, stats, gamma, M, H, dres_f32, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, dgamma,
                               dbeta, stream, dres_bf16, dx_res_bf16);
+}
+
+// ---- deterministic mode: the parameter-gradient forms with a partials workspace instead of float atomics ---------------------------------
+// One [2, H] partial per block of the PG grid (min(ceil(M / 4), 1024) blocks: a function of the shape only), then ordered_colsum_kernel
+// adds the rows in block order into dgamma / dbeta.
+extern "C" size_t clibd_layernorm_bwd_pg_workspace_bytes(int M, int H) {
+    if (M <= 0 || H <= 0) return 0;
+    return (size_t)min((M + 3) / 4, 1024) * 2 * (size_t)H * sizeof(float);
+}
+
+extern "C" int clibd_layernorm_bwd_pg_ordered(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
+                                              int M, int H, const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16,
+                                              void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* dx_fp8, float* row_dequant,
+                                              float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!dgamma || !dbeta) return set_error(CLIBD_EINVAL, "layernorm_bwd_pg_ordered: null dgamma / dbeta");
+    if (!workspace || ((uintptr_t)workspace & 15)) return set_error(CLIBD_EINVAL, "layernorm_bwd_pg_ordered: null or misaligned workspace");
+    if (M <= 0 || H <= 0 || workspace_bytes < clibd_layernorm_bwd_pg_workspace_bytes(M, H))
+        return set_error(CLIBD_EINVAL, "layernorm_bwd_pg_ordered: bad shape or workspace too small (clibd_layernorm_bwd_pg_workspace_bytes)");
+    return layernorm_bwd_impl(dy_bf16, dy_f32, x, stats, gamma, M, H, dres_f32, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, dgamma,
+                              dbeta, stream, dres_bf16, dx_res_bf16, dx_fp8, row_dequant, (float*)workspace);
 }

@@ -89,6 +89,20 @@ _NUMERICS_ENV = dict(residual_grad="CLIBD_RESIDUAL_GRAD", gelu_grad="CLIBD_GELU_
                      dgrad="CLIBD_DGRAD")
 
 
+def default_deterministic() -> bool:
+    """Deterministic training mode (opt-in; env CLIBD_DETERMINISTIC=1 gives a new stack / tower the default "on").  Not a numerics switch:
+    it changes no arithmetic, only the order of the reductions that would otherwise end in float atomics (LayerNorm / bias / embedding
+    parameter gradients, the adapters' gradients at token counts that are not whole 32-row slabs, split-K weight gradients): each takes a
+    partials workspace and a fixed-order second kernel (ops.*(ordered=True)), so a training step repeats bit for bit on one GPU.  Kept out
+    of NUMERICS_CHOICES (bench lines record those)."""
+    return os.environ.get("CLIBD_DETERMINISTIC", "0") == "1"
+
+
+def _ordered(on: bool) -> dict:
+    """keyword arguments selecting the fixed-order form of an ops reduction: none at all when the mode is off (calls stay as they were)"""
+    return {"ordered": True} if on else {}
+
+
 def default_numerics() -> dict:
     """The settings a new stack starts with: the first choice of each switch unless its environment variable names another."""
     out = {}
@@ -197,6 +211,7 @@ class TransformerStack:
         self.fp8 = None  # fp8-forward mode: [{site: activation scale}] per layer; see enable_fp8
         self._calib = None
         self.numerics = default_numerics()   # backward arithmetic switches (see NUMERICS_CHOICES above); set_numerics() changes them
+        self.deterministic = default_deterministic()   # fixed-order reductions in the backward (see default_deterministic)
         self._c2, self._c2_age = None, 0   # dgrad = "fp8" under full fine-tune: the per-layer d(fc1 out) scales and how many refreshes old they are
         self.dgrad8_sites = ("mlp", "proj")   # dgrad = "fp8": which of the covered GEMMs take it ("mlp" = the fc2 -> fc1 pair, "proj"); tools/dgrad8_sites_study.py
 
@@ -659,8 +674,10 @@ class TransformerStack:
         f8kw = lambda pair: dict(dx_fp8=pair[0], row_dequant=pair[1])
         dx8 = None
         # full fine-tune: the LayerNorm backward accumulates d(gamma), d(beta) in the same pass (it holds dy and xhat anyway)
-        pg = lambda w, b: (dict(dgamma=grads[id(w)].view(-1), dbeta=grads[id(b)].view(-1)) if full and id(w) in grads else {})
-        wg = lambda dy, x, ws, bs: linear_wgrad(dy, x, ws, bs, grads) if full else None
+        det = self.deterministic
+        pg = lambda w, b: (dict(dgamma=grads[id(w)].view(-1), dbeta=grads[id(b)].view(-1), **_ordered(det))
+                           if full and id(w) in grads else {})
+        wg = lambda dy, x, ws, bs: linear_wgrad(dy, x, ws, bs, grads, **_ordered(det)) if full else None
         for i in range(len(self.layers) - 1, -1, -1):
             L, c, rec = self.layers[i], self._cache[i], saved[i]
             has_lora = L.lora is not None
@@ -847,7 +864,7 @@ class TransformerStack:
         lp = L.lora
         r = lp.a_q.shape[0]
         if r == 4:
-            ops.lora_backward(dqkv, x_bf16, t, c.w_dt, dt, grads[id(lp.a_q)], grads[id(lp.a_v)], grads[id(lp.b_q)], grads[id(lp.b_v)])
+            ops.lora_backward(dqkv, x_bf16, t, c.w_dt, dt, grads[id(lp.a_q)], grads[id(lp.a_v)], grads[id(lp.b_q)], grads[id(lp.b_v)], **_ordered(self.deterministic))
             return None
         dev = dqkv.device
         dt2 = []
@@ -861,7 +878,7 @@ class TransformerStack:
                 dt2.append(dtk)
             ga_q, ga_v = torch.zeros((4, H), dtype=F32, device=dev), torch.zeros((4, H), dtype=F32, device=dev)
             gb_q, gb_v = torch.zeros((H, 4), dtype=F32, device=dev), torch.zeros((H, 4), dtype=F32, device=dev)
-            ops.lora_backward(dqkv, x_bf16, tk, w_dt, dtk, ga_q, ga_v, gb_q, gb_v)
+            ops.lora_backward(dqkv, x_bf16, tk, w_dt, dtk, ga_q, ga_v, gb_q, gb_v, **_ordered(self.deterministic))
             n = min(4, r - lo)   # the padded rows / columns receive exact zeros' worth of signal
             grads[id(lp.a_q)][lo:lo + n].add_(ga_q[:n]); grads[id(lp.a_v)][lo:lo + n].add_(ga_v[:n])
             grads[id(lp.b_q)][:, lo:lo + n].add_(gb_q[:, :n]); grads[id(lp.b_v)][:, lo:lo + n].add_(gb_v[:, :n])
@@ -869,11 +886,14 @@ class TransformerStack:
         return dt2
 
 
-def linear_wgrad(dy_bf16: torch.Tensor, x_bf16: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], grads: dict):
+def linear_wgrad(dy_bf16: torch.Tensor, x_bf16: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], grads: dict,
+                 ordered: bool = False):
     """Weight / bias gradients of y = x W^T + b for the parameters present in `grads` (accumulating):
     dW [N,K] += dy^T x — read in place by the rows-contracting kernel when the shape allows (M % 128 == 0, N and K % 256 == 0:
     every full-size layer), else as the NT GEMM (dy^T [N,Mp]) (x^T [K,Mp])^T over zero-padded transposes —
-    db += column sums of dy.  `weights` may be the row-wise pieces of a fused projection (BERT query / key / value)."""
+    db += column sums of dy.  `weights` may be the row-wise pieces of a fused projection (BERT query / key / value).
+    ordered (deterministic mode): every sum in a fixed order — the TN form's bias sums per slice, the generic GEMM unsplit (its split-K form
+    accumulates atomically), the column-sum kernel through partials."""
     if not any(id(w) in grads for w in weights) and not any(id(b) in grads for b in biases):
         return
     if x_bf16 is None:
@@ -895,7 +915,7 @@ def linear_wgrad(dy_bf16: torch.Tensor, x_bf16: torch.Tensor, weights: Sequence[
             took = False
             if pending[j]:
                 cs = grads[id(b)].view(-1) if wb else None
-                took = ops.gemm_tn_splitk(dy_bf16[:, n0:n1], x_bf16, grads[id(w)].view(w.shape[0], -1), accumulate=True, colsum=cs)
+                took = ops.gemm_tn_splitk(dy_bf16[:, n0:n1], x_bf16, grads[id(w)].view(w.shape[0], -1), accumulate=True, colsum=cs, **_ordered(ordered))
                 pending[j] = not took
             done.append(took and wb)
             n0 = n1
@@ -911,7 +931,7 @@ def linear_wgrad(dy_bf16: torch.Tensor, x_bf16: torch.Tensor, weights: Sequence[
         dyT = ops.transpose_bf16(dy_bf16, pad_to=128, colsum=csum)   # [N, Mp]
         xT = ops.transpose_bf16(x_bf16, pad_to=128)     # [K, Mp]
         Mp = dyT.shape[1]
-        split = max(1, min(32, Mp // 2048))
+        split = 1 if ordered else max(1, min(32, Mp // 2048))
         n0 = 0
         for j, w in enumerate(weights):
             n1 = n0 + w.shape[0]
@@ -937,7 +957,7 @@ def linear_wgrad(dy_bf16: torch.Tensor, x_bf16: torch.Tensor, weights: Sequence[
         for w, b, wb in zip(weights, biases, want_b):
             n1 = n0 + w.shape[0]
             if wb:
-                ops.colsum_bf16(dy_bf16[:, n0:n1], grads[id(b)])
+                ops.colsum_bf16(dy_bf16[:, n0:n1], grads[id(b)], **_ordered(ordered))
             n0 = n1
 
 
@@ -959,9 +979,9 @@ class GradBucket:
 
 
 def dense_head_backward(dout_f32: torch.Tensor, x_bf16: torch.Tensor, weight: torch.nn.Parameter, bias: torch.nn.Parameter,
-                        grads: dict, out_bf16: bool):
+                        grads: dict, out_bf16: bool, ordered: bool = False):
     """y = x W^T + b with a TRAINABLE W [D,K]:  dW += dy^T x, db += colsum(dy), returns dx = dy W.
-    dout_f32 [M,D] fp32 (M small: one row per sample) or bf16 [M,D]."""
+    dout_f32 [M,D] fp32 (M small: one row per sample) or bf16 [M,D].  ordered: fixed-order sums only (see linear_wgrad)."""
     dy_b = ops.cast_bf16(dout_f32) if dout_f32.dtype == F32 else dout_f32
     M, D = dy_b.shape
     K = x_bf16.shape[1]
@@ -969,7 +989,7 @@ def dense_head_backward(dout_f32: torch.Tensor, x_bf16: torch.Tensor, weight: to
     dyT = ops.transpose_bf16(dy_b, pad_to=128, colsum=grads[id(bias)].view(-1) if fused_bias else None)   # [D, Mp] (+ db)
     xT = ops.transpose_bf16(x_bf16, pad_to=128)         # [K, Mp]
     Mp = dyT.shape[1]
-    split = max(1, min(32, Mp // 2048))
+    split = 1 if ordered else max(1, min(32, Mp // 2048))
     gw = grads[id(weight)]
     if Mp >= 4096 and ops.gemm_nt_splitk(dyT, xT, gw, accumulate=True):
         pass  # long contraction (MLM decoder over all tokens): 256x256 split-K workspace path
@@ -978,7 +998,7 @@ def dense_head_backward(dout_f32: torch.Tensor, x_bf16: torch.Tensor, weight: to
     else:
         ops.gemm_nt(dyT, xT, out_f32=gw, residual=gw)        # accumulate in place
     if not fused_bias:
-        ops.colsum_bf16(dy_b, grads[id(bias)])
+        ops.colsum_bf16(dy_b, grads[id(bias)], **_ordered(ordered))
     w_t = ops.cast_transpose_bf16(_f32c(weight))   # [K, D]
     if out_bf16:
         dx = torch.empty((M, K), dtype=BF16, device=dy_b.device)

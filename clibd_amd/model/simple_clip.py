@@ -200,6 +200,20 @@ class SimpleCLIP(nn.Module):
             st.set_numerics(**settings)
         return self
 
+    def set_deterministic(self, enabled: bool = True):
+        """Deterministic training mode on every tower (clibd_amd.engine.default_deterministic): the backward's reductions run in a fixed
+        order, so the same parameters, batch and dropout seed give the same gradients bit for bit on one GPU.  Opt-in; the default comes from
+        CLIBD_DETERMINISTIC=1 when a tower is built.  Not part of numerics() (it changes the summation order only)."""
+        for enc in (self.image_encoder, self.dna_encoder, self.language_encoder):
+            if enc is not None and hasattr(enc, "tower"):
+                enc.tower().deterministic = bool(enabled)
+        return self
+
+    def deterministic(self) -> bool:
+        """True when every tower runs the deterministic mode."""
+        towers = [enc.tower() for enc in (self.image_encoder, self.dna_encoder, self.language_encoder) if enc is not None and hasattr(enc, "tower")]
+        return bool(towers) and all(t.deterministic for t in towers)
+
     def numerics(self) -> dict:
         """{tower: settings}: what produced this model's gradients (written into the bench line and the training state)."""
         out = {}

@@ -74,6 +74,26 @@ _STREAMK = os.environ.get("CLIBD_GEMM_STREAMK", "0") == "1"
 _TAIL_WS_BYTES = 48 * 1024 * 1024 + 1024
 _tail_ws: dict = {}
 
+# Deterministic mode (the `ordered=True` keyword of the reductions below): partials workspaces, one per (purpose, device, stream), grown on demand.
+# A workspace is only ever used by launches on its own stream, so stream order keeps consecutive users apart.
+_ordered_ws: dict = {}
+
+
+def _ordered_workspace(kind: str, nbytes: int, device) -> torch.Tensor:
+    key = (kind, device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _ordered_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
+        _ordered_ws[key] = ws
+    return ws
+
+
+def _not_ordered(what: str):
+    """the deterministic mode met a launch that only has an atomic form: an error, never a silent nondeterministic run"""
+    from .engine import NotSupportedYet
+
+    return NotSupportedYet(f"deterministic mode: {what} has no fixed-order form")
+
 
 def gemm_nt(
     a: torch.Tensor,
@@ -412,14 +432,18 @@ def layernorm_fwd(x, gamma, beta, eps, *, y_bf16=None, y_f32=None, stats=None, l
 
 
 def layernorm_bwd(dy, x, stats, gamma, *, dres=None, dx_f32=None, dx_bf16=None, drop=None, dgamma=None, dbeta=None,
-                  dres_bf16=None, dx_res_bf16=None, dx_fp8=None, row_dequant=None) -> None:
+                  dres_bf16=None, dx_res_bf16=None, dx_fp8=None, row_dequant=None, ordered: bool = False) -> None:
     """dgamma / dbeta (fp32 [H], accumulate): the LayerNorm parameter gradients in the same pass (full fine-tune mode).
     dres_bf16 / dx_res_bf16: the residual gradient travels as bf16 (clibd_layernorm_bwd_res16): dx = LN'(dy) + dres_bf16,
     dx_res_bf16 = bf16(dx) without the dropout mask that dx_bf16 carries; no fp32 input / output stream then.
     dx_fp8 [M,H] e4m3 + row_dequant [M] fp32 (8-bit dgrad, clibd_layernorm_bwd_fp8): the dx_bf16 values once more as the A operand of
-    gemm_fp8_dgrad_nt, one power-of-two scale per row; dx_bf16 itself becomes optional."""
+    gemm_fp8_dgrad_nt, one power-of-two scale per row; dx_bf16 itself becomes optional.
+    ordered (with dgamma / dbeta): the parameter gradients as per-block partials summed in block order (clibd_layernorm_bwd_pg_ordered)."""
     _chk(x, F32, "x")
     M, H = x.shape
+    if ordered and dgamma is not None:
+        _layernorm_bwd_pg_ordered(dy, x, stats, gamma, M, H, dres, dx_f32, dx_bf16, drop, dgamma, dbeta, dres_bf16, dx_res_bf16, dx_fp8, row_dequant)
+        return
     if dx_fp8 is not None or row_dequant is not None:
         if dx_fp8 is None or row_dequant is None or (dgamma is None) != (dbeta is None):
             raise ValueError("layernorm_bwd: dx_fp8 and row_dequant come together (and dgamma with dbeta)")
@@ -515,6 +539,36 @@ def layernorm_bwd(dy, x, stats, gamma, *, dres=None, dx_f32=None, dx_bf16=None, 
         return
     check(_lib.load().clibd_layernorm_bwd(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres), _p(dx_f32),
                                           _p(dx_bf16), _stream()), "layernorm_bwd")
+
+
+def _layernorm_bwd_pg_ordered(dy, x, stats, gamma, M, H, dres, dx_f32, dx_bf16, drop, dgamma, dbeta, dres_bf16, dx_res_bf16, dx_fp8, row_dequant):
+    if dbeta is None or (dx_fp8 is None) != (row_dequant is None):
+        raise ValueError("layernorm_bwd: dgamma with dbeta, dx_fp8 with row_dequant")
+    if dres is not None and dres_bf16 is not None:
+        raise ValueError("layernorm_bwd: the residual gradient is either fp32 (dres) or bf16 (dres_bf16)")
+    if dy.dtype not in (BF16, F32) or tuple(dy.shape) != (M, H):
+        raise ValueError("layernorm_bwd: dy must be bf16 or fp32 [M,H]")
+    _chk(dy, dy.dtype, "dy"); _chk(stats, F32, "stats"); _chk(gamma, F32, "gamma"); _chk(dgamma, F32, "dgamma"); _chk(dbeta, F32, "dbeta")
+    if dgamma.numel() != H or dbeta.numel() != H:
+        raise ValueError("layernorm_bwd: dgamma / dbeta must have H elements")
+    for nm, t, dt in (("dres", dres, F32), ("dres_bf16", dres_bf16, BF16), ("dx_f32", dx_f32, F32), ("dx_res_bf16", dx_res_bf16, BF16),
+                      ("dx_bf16", dx_bf16, BF16), ("dx_fp8", dx_fp8, FP8)):
+        if t is not None:
+            _chk(t, dt, nm)
+            if tuple(t.shape) != (M, H):
+                raise ValueError(f"layernorm_bwd: {nm} shape")
+    if row_dequant is not None:
+        _chk(row_dequant, F32, "row_dequant")
+        if row_dequant.numel() != M:
+            raise ValueError("layernorm_bwd: row_dequant must have M elements")
+    d = drop if (drop is not None and drop.thr16 > 0) else Drop(0.0, 0)
+    dyb, dyf = (dy.data_ptr(), None) if dy.dtype == BF16 else (None, dy.data_ptr())
+    lib = _lib.load()
+    need = int(lib.clibd_layernorm_bwd_pg_workspace_bytes(M, H))
+    ws = _ordered_workspace("ln_pg", need, x.device)
+    check(lib.clibd_layernorm_bwd_pg_ordered(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres), _p(dres_bf16), _p(dx_f32),
+                                             _p(dx_res_bf16), _p(dx_bf16), d.seed, d.thr16, d.scale, _p(dx_fp8), _p(row_dequant),
+                                             dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "layernorm_bwd_pg_ordered")
 
 
 def attention_fwd(qkv: torch.Tensor, B: int, S: int, nheads: int, key_mask: Optional[torch.Tensor], out: torch.Tensor,
@@ -652,9 +706,11 @@ def lora_wgrad(dqkv, x, t, dt, dA_q, dA_v, dB_q, dB_v, workspace=None) -> None:
                                        ws.data_ptr() if ws is not None else None, nb, _stream()), "lora_wgrad")
 
 
-def lora_backward(dqkv, x, t, w_dt, dt, dA_q, dA_v, dB_q, dB_v, workspace=None) -> None:
+def lora_backward(dqkv, x, t, w_dt, dt, dA_q, dA_v, dB_q, dB_v, workspace=None, ordered: bool = False) -> None:
     """dt = dqkv . w_dt^T (written, bf16 [M,16]) and the adapters' four parameter gradients (accumulated); see clibd_lora_backward.
-    workspace: None = a partials buffer is allocated (deterministic, atomics-free sums), a uint8 tensor = the caller's, False = float atomics."""
+    workspace: None = a partials buffer is allocated (deterministic, atomics-free sums), a uint8 tensor = the caller's, False = float atomics.
+    ordered: a token count that is not a multiple of 32 (which would take the VALU kernel and its float atomics) runs as whole 32-row slabs,
+    zero-padded — the padded rows contribute exact zeros to every sum; whole-slab counts run exactly as without it."""
     _chk(dqkv, BF16, "dqkv")
     _chk(x, BF16, "x")
     _chk(t, BF16, "t")
@@ -667,6 +723,18 @@ def lora_backward(dqkv, x, t, w_dt, dt, dA_q, dA_v, dB_q, dB_v, workspace=None) 
         _chk(g, F32, nm)
         if tuple(g.shape) != shape:
             raise ValueError(f"lora_backward: {nm} must be {shape}")
+    if ordered:
+        if workspace is False:
+            raise _not_ordered("lora_backward without a workspace")
+        if M % 32:
+            Mp = (M + 31) // 32 * 32
+            pad = lambda a: torch.cat([a, a.new_zeros((Mp - M, a.shape[1]))], dim=0)
+            dtp = torch.empty((Mp, 16), dtype=BF16, device=dt.device)
+            lora_backward(pad(dqkv), pad(x), pad(t), w_dt, dtp, dA_q, dA_v, dB_q, dB_v, workspace=None, ordered=True)
+            dt.copy_(dtp[:M])
+            return
+        if int(_lib.load().clibd_lora_workspace_bytes(M, H)) == 0:
+            raise _not_ordered(f"lora_backward at M={M}, H={H}")
     ws, nb = _lora_workspace(M, H, x.device, workspace)
     check(_lib.load().clibd_lora_backward(dqkv.data_ptr(), 3 * H, x.data_ptr(), t.data_ptr(), w_dt.data_ptr(), dt.data_ptr(), 16, M, H,
                                           dA_q.data_ptr(), dA_v.data_ptr(), dB_q.data_ptr(), dB_v.data_ptr(),
@@ -760,11 +828,16 @@ def token_mean_bwd(dout: torch.Tensor, S: int) -> torch.Tensor:
     return dx
 
 
-def colsum_bf16(x: torch.Tensor, out: torch.Tensor) -> None:
-    """out[N] (fp32) += column sums of x[M,N] (bf16)."""
+def colsum_bf16(x: torch.Tensor, out: torch.Tensor, ordered: bool = False) -> None:
+    """out[N] (fp32) += column sums of x[M,N] (bf16).  ordered: per-chunk partials summed in chunk order (clibd_colsum_bf16_ordered)."""
     _chk(x, BF16, "x", contiguous=False)
     _chk(out, F32, "out")
     M, N = x.shape
+    if ordered:
+        lib = _lib.load()
+        ws = _ordered_workspace("colsum", int(lib.clibd_colsum_workspace_bytes(M, N)), x.device)
+        check(lib.clibd_colsum_bf16_ordered(x.data_ptr(), _rowmajor(x, "x"), M, N, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "colsum_bf16_ordered")
+        return
     check(_lib.load().clibd_colsum_bf16(x.data_ptr(), _rowmajor(x, "x"), M, N, out.data_ptr(), _stream()), "colsum_bf16")
 
 
@@ -914,7 +987,7 @@ def kmer_tokenize(seq_u8: torch.Tensor, k: int = 5) -> torch.Tensor:
 
 # ------------------------------------------------------------------------------------------------ full fine-tune mode (f4)
 def layernorm_param_grads(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, dgamma: torch.Tensor, dbeta: torch.Tensor,
-                          drop: Optional[Drop] = None) -> None:
+                          drop: Optional[Drop] = None, ordered: bool = False) -> None:
     """dgamma += sum_m dy*xhat, dbeta += sum_m dy  (dy [M,H] bf16 or fp32; x fp32 [M,H]; stats fp32 [M,2])."""
     if dy.dtype not in (BF16, F32):
         raise TypeError("dy: expected bf16 or fp32")
@@ -924,23 +997,39 @@ def layernorm_param_grads(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor
     if tuple(dy.shape) != (M, H) or stats.numel() != 2 * M or dgamma.numel() != H or dbeta.numel() != H:
         raise ValueError("layernorm_param_grads: shape mismatch")
     d = drop if drop is not None else Drop(0.0, 0)
+    if ordered:
+        lib = _lib.load()
+        ws = _ordered_workspace("ln_param", int(lib.clibd_layernorm_param_grads_workspace_bytes(M, H)), x.device)
+        check(lib.clibd_layernorm_param_grads_ordered(dy.data_ptr(), int(dy.dtype == F32), _rowmajor(dy, "dy"), x.data_ptr(), stats.data_ptr(), M, H,
+                                                      dgamma.data_ptr(), dbeta.data_ptr(), d.seed, d.thr16, d.scale, ws.data_ptr(), ws.numel(), _stream()),
+              "layernorm_param_grads_ordered")
+        return
     check(_lib.load().clibd_layernorm_param_grads(dy.data_ptr(), int(dy.dtype == F32), _rowmajor(dy, "dy"), x.data_ptr(), stats.data_ptr(), M, H,
                                                   dgamma.data_ptr(), dbeta.data_ptr(), d.seed, d.thr16, d.scale, _stream()), "layernorm_param_grads")
 
 
-def batch_sum(x: torch.Tensor, out: torch.Tensor) -> None:
-    """out[...] += x.sum(0)   (x fp32 [B, ...], out fp32 with x.shape[1:] elements)."""
+def batch_sum(x: torch.Tensor, out: torch.Tensor, ordered: bool = False) -> None:
+    """out[...] += x.sum(0)   (x fp32 [B, ...], out fp32 with x.shape[1:] elements).  ordered: per-chunk partials, summed in chunk order."""
     _chk(x, F32, "x"); _chk(out, F32, "out")
     B = x.shape[0]
     R = x.numel() // B
     if out.numel() != R:
         raise ValueError("batch_sum: out must have x.numel() / B elements")
+    if ordered:
+        if not out.is_contiguous():
+            raise ValueError("batch_sum: out must be contiguous")
+        lib = _lib.load()
+        ws = _ordered_workspace("batch_sum", int(lib.clibd_batch_sum_workspace_bytes(B, R)), x.device)
+        check(lib.clibd_batch_sum_f32_ordered(x.data_ptr(), B, R, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "batch_sum_ordered")
+        return
     check(_lib.load().clibd_batch_sum_f32(x.data_ptr(), B, R, out.data_ptr(), _stream()), "batch_sum")
 
 
 def bert_embed_bwd(ids: torch.Tensor, token_type: Optional[torch.Tensor], de: torch.Tensor, dword: Optional[torch.Tensor],
-                   dtype_table: Optional[torch.Tensor]) -> None:
-    """Scatter the embedding gradient de [M,H] into the word table (by ids) and the token-type table (accumulating)."""
+                   dtype_table: Optional[torch.Tensor], ordered: bool = False) -> None:
+    """Scatter the embedding gradient de [M,H] into the word table (by ids) and the token-type table (accumulating).
+    ordered: the word table through a stable sort of (id, row) and per-id sums in row order, the token-type table (at most two types)
+    through per-block partials (clibd_bert_embed_bwd_ordered)."""
     _chk(ids, torch.int64, "ids"); _chk(de, F32, "de")
     M, H = de.shape
     if ids.numel() != M:
@@ -952,6 +1041,14 @@ def bert_embed_bwd(ids: torch.Tensor, token_type: Optional[torch.Tensor], de: to
     for t, n in ((dword, "dword"), (dtype_table, "dtype")):
         if t is not None:
             _chk(t, F32, n)
+    if ordered:
+        if tv > 2:
+            raise _not_ordered(f"bert_embed_bwd with {tv} token types")
+        lib = _lib.load()
+        ws = _ordered_workspace("embed", int(lib.clibd_bert_embed_bwd_workspace_bytes(M, H, vocab, tv)), de.device)
+        check(lib.clibd_bert_embed_bwd_ordered(ids.data_ptr(), _p(token_type), de.data_ptr(), M, H, vocab, tv, _p(dword), _p(dtype_table),
+                                               ws.data_ptr(), ws.numel(), _stream()), "bert_embed_bwd_ordered")
+        return
     check(_lib.load().clibd_bert_embed_bwd(ids.data_ptr(), _p(token_type), de.data_ptr(), M, H, vocab, tv, _p(dword), _p(dtype_table), _stream()),
           "bert_embed_bwd")
 
@@ -976,10 +1073,11 @@ def dropout_apply(x: torch.Tensor, drop: Drop) -> torch.Tensor:
 _splitk_ws = {}
 
 
-def gemm_tn_splitk(a: torch.Tensor, b: torch.Tensor, out_f32: torch.Tensor, accumulate: bool = True, colsum: Optional[torch.Tensor] = None) -> bool:
+def gemm_tn_splitk(a: torch.Tensor, b: torch.Tensor, out_f32: torch.Tensor, accumulate: bool = True, colsum: Optional[torch.Tensor] = None,
+                   ordered: bool = False) -> bool:
     """out[Na,Nb] (+)= a[M,Na]^T @ b[M,Nb], both operands read in place (clibd_gemm_bf16_tn_splitk): the weight gradient
     dW = dy^T x without transposes; colsum (fp32 [Na]) += column sums of a in the same pass (the bias gradient).
-    Returns False (nothing launched) when the shape is outside the kernel's."""
+    Returns False (nothing launched) when the shape is outside the kernel's.  ordered: the column sums per M-slice, summed in slice order."""
     _chk(a, BF16, "a", contiguous=False); _chk(b, BF16, "b", contiguous=False); _chk(out_f32, F32, "out_f32")
     M, Na = a.shape
     Nb = b.shape[1]
@@ -998,8 +1096,13 @@ def gemm_tn_splitk(a: torch.Tensor, b: torch.Tensor, out_f32: torch.Tensor, accu
         _chk(colsum, F32, "colsum")
         if colsum.numel() != Na:
             raise ValueError("gemm_tn_splitk: colsum must have Na elements")
-    rc = lib.clibd_gemm_bf16_tn_splitk(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), M, Na, Nb, out_f32.data_ptr(), Nb,
-                                       int(accumulate), _p(colsum), ws.data_ptr(), ws.numel() * 4, _stream())
+    if ordered and colsum is not None:
+        cws = _ordered_workspace("tn_colsum", int(lib.clibd_gemm_tn_colsum_workspace_bytes(M, Na)), a.device)
+        rc = lib.clibd_gemm_bf16_tn_splitk_ordered(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), M, Na, Nb, out_f32.data_ptr(), Nb,
+                                                   int(accumulate), colsum.data_ptr(), ws.data_ptr(), ws.numel() * 4, cws.data_ptr(), cws.numel(), _stream())
+    else:
+        rc = lib.clibd_gemm_bf16_tn_splitk(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), M, Na, Nb, out_f32.data_ptr(), Nb,
+                                           int(accumulate), _p(colsum), ws.data_ptr(), ws.numel() * 4, _stream())
     if rc != 0 and b"shape not supported" in (lib.clibd_last_error() or b""):
         return False    # declined before anything was enqueued: the caller takes the transpose + NT path
     check(rc, "gemm_bf16_tn_splitk")

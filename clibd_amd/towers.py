@@ -13,7 +13,7 @@ from typing import List, Optional
 import torch
 
 from . import ops
-from .engine import BF16, F32, GradBucket, LayerSpec, LoraParams, NotSupportedYet, TransformerStack, _f32c, dense_head_backward, linear_wgrad
+from .engine import BF16, F32, GradBucket, LayerSpec, LoraParams, NotSupportedYet, TransformerStack, _f32c, _ordered, dense_head_backward, linear_wgrad
 
 
 def _trainable(params):
@@ -76,6 +76,15 @@ class _Tower:
         for attr in ("_patch_key", "_head_key"):
             if hasattr(self, attr):
                 setattr(self, attr, None)
+
+    @property
+    def deterministic(self) -> bool:
+        """fixed-order reductions in this tower's backward (engine.default_deterministic); one setting for the stack and the tower's own code"""
+        return self.stack.deterministic
+
+    @deterministic.setter
+    def deterministic(self, on: bool):
+        self.stack.deterministic = bool(on)
 
     def _stack_groups(self, head, embed):
         n = len(self.stack.layers)
@@ -184,13 +193,14 @@ class ViTTower(_Tower):
         v, B, S, H = self.vit, state["B"], 197, self.H
         head = v.head
         if isinstance(head, torch.nn.Linear):
-            dxn = dense_head_backward(dout, state["xn"], head.weight, head.bias, grads, out_bf16=True)
+            dxn = dense_head_backward(dout, state["xn"], head.weight, head.bias, grads, out_bf16=True, **_ordered(self.deterministic))
         else:
             dxn = ops.cast_bf16(dout)
         dxcls = torch.empty((B, H), dtype=F32, device=dout.device)
         dxcls_b = torch.empty((B, H), dtype=BF16, device=dout.device)
         full = state["full"]
-        pg = dict(dgamma=grads[id(v.norm.weight)].view(-1), dbeta=grads[id(v.norm.bias)].view(-1)) if full and id(v.norm.weight) in grads else {}
+        det = self.deterministic
+        pg = dict(dgamma=grads[id(v.norm.weight)].view(-1), dbeta=grads[id(v.norm.bias)].view(-1), **_ordered(det)) if full and id(v.norm.weight) in grads else {}
         ops.layernorm_bwd(dxn, state["xcls"], state["st"], _f32c(v.norm.weight), dx_f32=dxcls, dx_bf16=dxcls_b, **pg)
         self._ready(0)
         nl = len(self.stack.layers)
@@ -200,12 +210,12 @@ class ViTTower(_Tower):
             # tokens = [cls + pos[0] | patch_proj + pos[1:]]  (timm VisionTransformer._pos_embed)
             d3 = dtok.view(B, S, H)
             if id(v.pos_embed) in grads:
-                ops.batch_sum(d3, grads[id(v.pos_embed)])
+                ops.batch_sum(d3, grads[id(v.pos_embed)], **_ordered(det))
             if id(v.cls_token) in grads:
-                ops.batch_sum(ops.gather_rows(d3), grads[id(v.cls_token)])
+                ops.batch_sum(ops.gather_rows(d3), grads[id(v.cls_token)], **_ordered(det))
             pw, pb = v.patch_embed.proj.weight, v.patch_embed.proj.bias
             if id(pw) in grads or id(pb) in grads:
-                linear_wgrad(ops.slice_rows_cast_bf16(d3, 1, S), state["patches"], [pw], [pb], grads)
+                linear_wgrad(ops.slice_rows_cast_bf16(d3, 1, S), state["patches"], [pw], [pb], grads, **_ordered(det))
 
 
 # =========================================================================================================
@@ -352,24 +362,25 @@ class BertTower(_Tower):
         B, S, H = state["B"], state["S"], self.H
         M = B * S
         dev = dout.device
+        det = self.deterministic
         if self.head_kind == "mlm":
             _, wt_t = self._head_images()
             tln, dec = self.hm["transform_ln"], self.hm["decoder"]
             dlogits = ops.softmax_mean_bwd(state["logits"], dout, B, S)
-            dhln = dense_head_backward(dlogits, state["hln"], dec.weight, dec.bias, grads, out_bf16=True)
+            dhln = dense_head_backward(dlogits, state["hln"], dec.weight, dec.bias, grads, out_bf16=True, **_ordered(det))
             full = state["full"]
-            pg = dict(dgamma=grads[id(tln.weight)].view(-1), dbeta=grads[id(tln.bias)].view(-1)) if full and id(tln.weight) in grads else {}
+            pg = dict(dgamma=grads[id(tln.weight)].view(-1), dbeta=grads[id(tln.bias)].view(-1), **_ordered(det)) if full and id(tln.weight) in grads else {}
             dg = torch.empty((M, H), dtype=BF16, device=dev)
             ops.layernorm_bwd(dhln, state["g"], state["st"], _f32c(tln.weight), dx_bf16=dg, **pg)
             dhpre = ops.gelu_bwd(dg, state["hpre"])
             if full:
                 td = self.hm["transform_dense"]
-                linear_wgrad(dhpre, state["x_top"], [td.weight], [td.bias], grads)
+                linear_wgrad(dhpre, state["x_top"], [td.weight], [td.bias], grads, **_ordered(det))
             dx = torch.empty((M, H), dtype=F32, device=dev)
             ops.gemm_nt(dhpre, wt_t, out_f32=dx)
         else:
             proj = self.hm["proj"]
-            dmean = dense_head_backward(dout, state["mean"], proj.weight, proj.bias, grads, out_bf16=False)
+            dmean = dense_head_backward(dout, state["mean"], proj.weight, proj.bias, grads, out_bf16=False, **_ordered(det))
             dx = ops.token_mean_bwd(dmean, S).view(M, H)
         full = state["full"]
         self._ready(0)
@@ -381,7 +392,7 @@ class BertTower(_Tower):
             lw, lb = emb.LayerNorm.weight, emb.LayerNorm.bias
             if state["d_emb"] is not None and state["d_emb"].thr16 > 0:
                 dx0 = ops.dropout_apply(dx0, state["d_emb"])  # gradient w.r.t. the LayerNorm output
-            pg = dict(dgamma=grads[id(lw)].view(-1), dbeta=grads[id(lb)].view(-1)) if id(lw) in grads else {}
+            pg = dict(dgamma=grads[id(lw)].view(-1), dbeta=grads[id(lb)].view(-1), **_ordered(det)) if id(lw) in grads else {}
             tabs = [emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight]
             need_de = any(id(t) in grads for t in tabs)
             if need_de or pg:
@@ -389,6 +400,6 @@ class BertTower(_Tower):
                 ops.layernorm_bwd(dx0, state["e"], state["st_e"], _f32c(lw), dx_f32=de, **pg)   # + d(gamma), d(beta) in the same pass
             if need_de:
                 if id(tabs[1]) in grads:
-                    ops.batch_sum(de.view(B, S * H), grads[id(tabs[1])][:S])
+                    ops.batch_sum(de.view(B, S * H), grads[id(tabs[1])][:S], **_ordered(det))
                 ops.bert_embed_bwd(state["ids"].view(-1), None if state["tt"] is None else state["tt"].view(-1), de,
-                                   grads.get(id(tabs[0])), grads.get(id(tabs[2])))
+                                   grads.get(id(tabs[0])), grads.get(id(tabs[2])), **_ordered(det))

@@ -70,7 +70,7 @@ class Trainer:
     def __init__(self, model, lr: float = 1e-3, world_size: int = 1, rank: int = 0, all_gather: bool = True,
                  fix_temperature: Optional[float] = None, bind_to=None, no_image_text_loss=False, weight_decay: float = 1e-2,
                  broadcast_parameters: bool = True, bucket_bytes: int = 64 << 20, fp8_recalibrate_every: int = 0,
-                 numerics: Optional[dict] = None):
+                 numerics: Optional[dict] = None, deterministic: Optional[bool] = None):
         """bucket_bytes: at world_size > 1, when the gradients are at least two buckets long (full fine-tune: 694 MB), the
         all-reduce is issued in pieces of about this size as the backward completes them, each on the stream that produced
         it, so RCCL runs under the rest of the backward; smaller gradient sets (LoRA: 6 MB) keep the single all-reduce.
@@ -78,10 +78,14 @@ class Trainer:
         scales on the incoming batch before steps 0, N, 2N, ... (one extra bf16 forward each time), so the static scales of
         a long run follow the activations as the adapters train.
         numerics: backward arithmetic switches for every tower of `model` (clibd_amd.engine.NUMERICS_CHOICES); None keeps what the
-        towers were constructed with (environment defaults)."""
+        towers were constructed with (environment defaults).
+        deterministic: True / False turns the deterministic training mode on / off on every tower (SimpleCLIP.set_deterministic: fixed-order
+        reductions, a step repeats bit for bit on one GPU; RCCL's all-reduce order across ranks is not covered); None keeps the model's setting."""
         self.model, self.world_size, self.rank = model, world_size, rank
         if numerics:    # e.g. dict(residual_grad="fp32"): the reference's fp32 residual-gradient stream (engine.NUMERICS_CHOICES)
             model.set_numerics(**numerics)
+        if deterministic is not None:
+            model.set_deterministic(bool(deterministic))
         # the data-parallel path: world_size > 1, or a one-rank group under CLIBD_FORCE_COLLECTIVES=1 (tests: RCCL on a 1-GPU box)
         self._dist = world_size > 1 or collectives_forced()
         self.fix_temperature = fix_temperature

@@ -466,6 +466,36 @@ int clibd_bert_embed_bwd(const int64_t* ids, const int64_t* token_type, const fl
 /* out bf16 [B*(s1-s0), H] = rows s0..s1-1 of every sequence of x fp32 [B,S,H] (patch rows of the ViT token gradient). */
 int clibd_slice_rows_cast_bf16(const float* x, int B, int S, int H, int s0, int s1, void* out, void* stream);
 
+/* ---- deterministic mode (ABI 5, additive): the forms above without float atomics.  Each writes one partial per block / slice / chunk into
+ * a caller-owned workspace (size from its *_workspace_bytes query; 16-byte aligned) and a second kernel adds the partials in a fixed order
+ * (block, slice, chunk order), so that the result depends on the inputs and the shape only and repeats bit for bit.  Outputs ACCUMULATE as
+ * in the atomic forms; nothing allocates; everything is enqueued on `stream`.  A null or short workspace returns -1. */
+/* clibd_layernorm_bwd_any / clibd_layernorm_bwd_fp8_pg with the parameter gradients summed in block order (dgamma, dbeta required;
+ * dx_fp8 / row_dequant optional, together). */
+size_t clibd_layernorm_bwd_pg_workspace_bytes(int M, int H);
+int clibd_layernorm_bwd_pg_ordered(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
+                                   int M, int H, const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16,
+                                   void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* dx_fp8, float* row_dequant,
+                                   float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+size_t clibd_layernorm_param_grads_workspace_bytes(int M, int H);
+int clibd_layernorm_param_grads_ordered(const void* dy, int dy_is_f32, int ld_dy, const float* x, const float* stats, int M, int H,
+                                        float* dgamma, float* dbeta, uint32_t drop_seed, int drop_thr16, float drop_scale,
+                                        void* workspace, size_t workspace_bytes, void* stream);
+size_t clibd_batch_sum_workspace_bytes(int B, size_t R);
+int clibd_batch_sum_f32_ordered(const float* x, int B, size_t R, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* word table: a stable radix sort of (id, row), then per-id sums in row order (long lists cut into fixed chunks whose partials are added
+ * in chunk order); token-type table (type_vocab <= 2): per-block partials.  vocab <= 2^24. */
+size_t clibd_bert_embed_bwd_workspace_bytes(int M, int H, int vocab, int type_vocab);
+int clibd_bert_embed_bwd_ordered(const int64_t* ids, const int64_t* token_type, const float* de, int M, int H, int vocab, int type_vocab,
+                                 float* dword, float* dtype, void* workspace, size_t workspace_bytes, void* stream);
+size_t clibd_colsum_workspace_bytes(int M, int N);
+int clibd_colsum_bf16_ordered(const void* x, int ld, int M, int N, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* clibd_gemm_bf16_tn_splitk with colsum_a (required) stored per M-slice into colsum_workspace and summed in slice order. */
+size_t clibd_gemm_tn_colsum_workspace_bytes(int M, int Na);
+int clibd_gemm_bf16_tn_splitk_ordered(const void* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* out_f32, int ld_out,
+                                      int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
+                                      size_t colsum_workspace_bytes, void* stream);
+
 /* fused AdamW step on a flat fp32 parameter bucket (torch.optim.AdamW semantics, scripts/train_cl.py:221):
  * p,g,m,v [n]; g is multiplied by grad_scale first (1/world_size folding etc.). */
 int clibd_adamw_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1,
