@@ -11,7 +11,11 @@ bases, adapter + head gradients), flat-bucket gradient all-reduce and fused Adam
 (BASELINE.json `metric`: "global batch 2048, 1/2/4/8 GPU"): per-GPU batch = 2048 / N, so N=1 runs b=2048 on one GPU
 and N=8 is BASELINE configs[2] (b=256 per GPU) — strong scaling.  `--per-gpu-batch 256` gives BASELINE configs[1].
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the bf16 MFMA GEMM): algorithmic FLOPs of every
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, `--warmup` steps, the `--steps`
+timed steps, `--dump-outputs`, the line.  `--full` adds, after the timed steps, every side measurement of the line (each of them
+can still be dropped with its `--no-*` switch): the GEMM timing passes behind `roofline.achieved` / `frac` (and
+`--gemm-breakdown`), `reference_numerics`, `h2d_inclusive`, `configs4`, `cpu_baseline`, the collective diagnostics at N > 1
+and the `--eval` top-k search.  `roofline` is for the dominant kernel (the bf16 MFMA GEMM): algorithmic FLOPs of every
 GEMM launch in the timed region / their summed HIP-event durations on the launch stream, against the 2.5 PFLOP/s
 dense bf16 peak.  `cpu_baseline` is the CPU oracle's training step (oracle/clibd_oracle.py, the reference's CPU path
 restated and pinned to it) timed on this host's cores with a bounded sample, rank 0, N=1 only.
@@ -70,7 +74,16 @@ def parse():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all): training = "
                          "loss, params, grads; --eval = the embeddings.  Inputs are seeded, so two builds can be compared output for output")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the timed steps (the --no-* switches above drop single ones): GEMM timing passes "
+                         "(roofline achieved / frac), reference_numerics, h2d_inclusive, configs4, cpu_baseline, the collective diagnostics at N > 1, "
+                         "the --eval top-k search.  Without it a run sets up, warms up, times --steps, writes --dump-outputs and prints its line")
+    args = ap.parse_args()
+    if args.gemm_breakdown and not args.full:
+        ap.error("--gemm-breakdown prints the GEMM timing passes, which run under --full")
+    if not args.full:   # a plain run: the headline only
+        args.no_gemm_timing = args.no_ref_numerics = args.no_h2d = args.no_configs4 = args.no_cpu_baseline = True
+    return args
 
 
 DUMP_MAX_ELEMS = 4 << 20   # per dumped array (16 MB of fp32): at most three such arrays plus the loss stay under 64 MB
@@ -443,7 +456,7 @@ def eval_bench(args, model, batch, b, world, rank, dev, dist, timer):
         gemm = timer.result()
         gemm["steps"] = min(args.steps, 5)
     k10 = None
-    if rank == 0:
+    if rank == 0 and args.full:
         Q, Nk, D, k = min(args.eval_queries, b), args.eval_keys, out[0].shape[1], 5
         g = torch.Generator(device=dev).manual_seed(7)
         keys = torch.nn.functional.normalize(torch.randn((Nk, D), generator=g, device=dev), dim=1)
@@ -802,7 +815,7 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
     ctimer = None
-    if world > 1 or forced:
+    if (world > 1 or forced) and args.full:
         ctimer = CollectiveTimer()
         ctimer.install(dist)   # before clibd_amd.model / .train bind `dist` (they call through the module attribute)
 

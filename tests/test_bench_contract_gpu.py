@@ -1,11 +1,13 @@
 """bench.py's output contract on a GPU box: ONE line on stdout, a JSON object with the driver's keys, also when a process group
 exists (librccl prints a version banner to fd 1 when the group is created; bench.py points fd 1 at stderr and writes its line to
-the saved descriptor).  Small per-GPU batch so the check takes seconds."""
+the saved descriptor).  Small per-GPU batch so the check takes seconds.  A plain run carries the headline only; the side records
+ride in the line of a `--full` run."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -16,8 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("forced", ["0", "1"])
 def test_bench_prints_exactly_one_json_line(forced):
     env = dict(os.environ, CLIBD_FORCE_COLLECTIVES=forced)
-    # (the forced-collectives run skips the host-batch legs; the plain run keeps them: round 5's steady-state / uint8 legs are part of the line)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--per-gpu-batch", "32", "--steps", "2", "--warmup", "1",
+    # (the forced-collectives run skips the host-batch legs; the other keeps them: round 5's steady-state / uint8 legs are part of the --full line)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--per-gpu-batch", "32", "--steps", "2", "--warmup", "1",
                         "--no-cpu-baseline", "--configs4-batch", "32"] + (["--no-h2d"] if forced == "1" else []), capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     if forced == "1" and r.returncode != 0 and "init_process_group" in r.stderr:
         pytest.skip("one-rank RCCL process group unavailable on this box")
@@ -84,7 +86,7 @@ def test_bench_line_of_the_fp8_configuration():
     """BASELINE configs[4] as bench.py runs it (`--fp8-forward pooled --dgrad fp8`): the line says so in dtype / config, it is a secondary
     config (never the metric's), the numerics record carries dgrad = fp8 for both towers and the fp8 forward for the pooled tower only, and
     the roofline prices the fp8 launches (forward and 8-bit dgrad) at the fp8 peak."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--per-gpu-batch", "32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--per-gpu-batch", "32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                         "--no-h2d", "--fp8-forward", "pooled", "--dgrad", "fp8"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -96,3 +98,27 @@ def test_bench_line_of_the_fp8_configuration():
     assert num["image_encoder"]["forward"] == "bf16" and num["dna_encoder"]["forward"].startswith("fp8")
     assert d["value"] > 0 and d["loss"] == d["loss"] and "reference_numerics" not in d
     assert 0 < d["roofline"]["frac"] < 1 and 0.2 < d["roofline"]["fp8_flop_share"] < 0.9   # DNA forward + MLP / projection dgrads of both towers
+
+
+def test_plain_run_prints_the_headline_only(tmp_path):
+    """Without --full: set-up, warm-up, the timed steps, --dump-outputs and the line — the headline keys as a --full line carries them,
+    no side record and no GEMM timing pass (roofline without achieved / frac)."""
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--per-gpu-batch", "32", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[:2000]
+    d = json.loads(lines[0])
+    assert d["metric"] == "paired samples/sec/step (I+D contrastive), global batch 32" and d["unit"] == "paired samples/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "bf16" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+    assert d["config"]["train_mode"] is True and all(v["forward"] == "bf16" and v["dgrad"] == "bf16" for v in d["config"]["numerics"].values())
+    for k in ("reference_numerics", "h2d_inclusive", "configs4", "cpu_baseline", "collectives_ms", "per_rank_ms"):
+        assert k not in d, k
+    roof = d["roofline"]
+    assert roof["achieved"] is None and roof["frac"] is None and "launches" not in roof and roof["step_frac"] > 0
+    assert sorted(os.listdir(out_dir)) == ["grads.npy", "loss.npy", "params.npy"]
+    loss = np.load(out_dir / "loss.npy")
+    assert loss.shape == (1,) and float(loss[0]) == pytest.approx(d["loss"], rel=1e-6)
+    assert np.load(out_dir / "params.npy").shape == np.load(out_dir / "grads.npy").shape

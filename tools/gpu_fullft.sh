@@ -2,10 +2,10 @@
 # full fine-tune (model_config.disable_lora) profile at a given per-GPU batch
 set -u
 B=${1:-256}; OUT=gpurun_out/fullft_b$B; mkdir -p $OUT; export TMPDIR=/tmp
-timeout 600 python bench.py --full-finetune --per-gpu-batch $B --steps 10 --warmup 3 --no-cpu-baseline --no-h2d --gemm-breakdown > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --full-finetune --per-gpu-batch $B --steps 10 --warmup 3 --no-cpu-baseline --no-h2d --gemm-breakdown > $OUT/bench.json 2> $OUT/bench.err
 tail -c 900 $OUT/bench.json; echo
 export CLIBD_TOWER_STREAMS=0
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_serial -- python3 bench.py --full-finetune --per-gpu-batch $B --steps 5 --warmup 2 --no-cpu-baseline --no-gemm-timing --no-h2d > $OUT/prof.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_serial -- python3 bench.py --full --full-finetune --per-gpu-batch $B --steps 5 --warmup 2 --no-cpu-baseline --no-gemm-timing --no-h2d > $OUT/prof.log 2>&1
 find $OUT -name "*kernel_trace.csv" -size +20M -delete; find $OUT -name "*.db" -delete
 python - <<PY
 import csv,glob

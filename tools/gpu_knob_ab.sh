@@ -10,7 +10,7 @@ if [ -z "$NOTEST" ]; then
   timeout 1500 python -m pytest tests -m gpu -q --maxfail=20 -p no:cacheprovider > "$OUT/pytest_gpu.log" 2>&1; echo "pytest exit $?"; tail -15 "$OUT/pytest_gpu.log"
 fi
 for mode in $A $B $A $B; do
-  env $KNOB=$mode timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-h2d --gemm-breakdown > "$OUT/bench_$mode.json" 2> "$OUT/bench_$mode.err"
+  env $KNOB=$mode timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-h2d --gemm-breakdown > "$OUT/bench_$mode.json" 2> "$OUT/bench_$mode.err"
   echo "bench $mode exit $?"; python - "$OUT/bench_$mode.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]; b = r.get("board") or {}

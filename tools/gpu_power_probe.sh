@@ -14,7 +14,7 @@ cat "$OUT/shapes.log"
 python tools/power_sampler.py "$OUT/power_step.txt" 100 0.05 &
 S2=$!
 date +%s.%N > "$OUT/step_t0.txt"
-timeout 600 python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-h2d > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-h2d > "$OUT/bench.json" 2> "$OUT/bench.err"
 date +%s.%N > "$OUT/step_t1.txt"
 kill $S2 2>/dev/null; wait $S2 2>/dev/null
 tail -c 400 "$OUT/bench.json"

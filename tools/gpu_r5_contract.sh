@@ -5,7 +5,7 @@ OUT=gpurun_out/${1:-r5c}
 mkdir -p "$OUT"
 timeout -k 10 600 python -m pytest tests/test_bench_contract_gpu.py -m gpu -q -x -p no:cacheprovider > "$OUT/pytest.log" 2>&1
 echo "pytest exit $?"; tail -2 "$OUT/pytest.log"
-CLIBD_BENCH_SHARED_GPU=1 timeout -k 10 400 python bench.py --gpus 2 --global-batch 512 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench_w2_shared.json" 2> "$OUT/bench_w2_shared.err"
+CLIBD_BENCH_SHARED_GPU=1 timeout -k 10 400 python bench.py --full --gpus 2 --global-batch 512 --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench_w2_shared.json" 2> "$OUT/bench_w2_shared.err"
 echo "w2 exit $?"; python - "$OUT/bench_w2_shared.json" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

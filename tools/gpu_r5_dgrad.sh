@@ -12,7 +12,7 @@ for cfg in $CFGS; do
   fw=${cfg%%:*}; dg=${cfg##*:}; i=$((i+1))
   if [ "$fw" = "bf16" ]; then FLAG=""; else FLAG="--fp8-forward $fw"; fi
   name="${i}_${fw}_dgrad_${dg}_b${B}"
-  timeout -k 10 300 python bench.py $FLAG --dgrad $dg --per-gpu-batch $B --steps 10 --warmup 3 --no-cpu-baseline --no-h2d --no-ref-numerics --gemm-breakdown > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" \
+  timeout -k 10 300 python bench.py --full $FLAG --dgrad $dg --per-gpu-batch $B --steps 10 --warmup 3 --no-cpu-baseline --no-h2d --no-ref-numerics --gemm-breakdown > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" \
     && python - "$OUT/bench_$name.json" "$name" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -21,7 +21,7 @@ PY
 done
 if [ "${4:-}" = "prof" ]; then   # kernel statistics of the pooled forward + 8-bit dgrad step, serial towers
   export CLIBD_TOWER_STREAMS=0
-  CMD="python3 bench.py --fp8-forward pooled --dgrad fp8 --per-gpu-batch $B --steps 5 --warmup 2 --no-cpu-baseline --no-gemm-timing --no-h2d --no-ref-numerics"
+  CMD="python3 bench.py --full --fp8-forward pooled --dgrad fp8 --per-gpu-batch $B --steps 5 --warmup 2 --no-cpu-baseline --no-gemm-timing --no-h2d --no-ref-numerics"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_dgrad8" -- $CMD > "$OUT/prof_dgrad8.log" 2>&1
   echo "prof exit $?"
   unset CLIBD_TOWER_STREAMS

@@ -5,7 +5,7 @@ OUT=gpurun_out/${1:-rcs}
 mkdir -p "$OUT"
 run() {  # name, env...
   local name=$1; shift
-  env "$@" timeout 600 python bench.py ${CLIBD_BENCH_EXTRA:-} --steps 8 --warmup 3 --no-cpu-baseline --no-h2d --no-gemm-timing > "$OUT/$name.json" 2> "$OUT/$name.err"
+  env "$@" timeout 600 python bench.py --full ${CLIBD_BENCH_EXTRA:-} --steps 8 --warmup 3 --no-cpu-baseline --no-h2d --no-gemm-timing > "$OUT/$name.json" 2> "$OUT/$name.err"
   python - "$OUT/$name.json" "$name" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 for mode in 0 1; do
   export CLIBD_FORCE_COLLECTIVES=$mode
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace$mode" -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-gemm-timing --no-h2d > "$OUT/trace$mode.log" 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace$mode" -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-gemm-timing --no-h2d > "$OUT/trace$mode.log" 2>&1
   echo "mode $mode exit $?"
   python tools/trace_gaps.py "$OUT/trace$mode" 2 > "$OUT/gaps$mode.txt" 2>&1; cat "$OUT/gaps$mode.txt"
   python - "$OUT/trace$mode" <<'PY'

@@ -13,22 +13,22 @@ if has test; then
   echo "pytest exit $?" >> "$OUT/pytest_gpu.log"; tail -5 "$OUT/pytest_gpu.log"
 fi
 if has bench; then
-  timeout 900 python bench.py --steps 10 --warmup 3 --gemm-breakdown > "$OUT/bench_b2048.json" 2> "$OUT/bench_b2048.err"
+  timeout 900 python bench.py --full --steps 10 --warmup 3 --gemm-breakdown > "$OUT/bench_b2048.json" 2> "$OUT/bench_b2048.err"
   echo "bench exit $?"; tail -c 1500 "$OUT/bench_b2048.json"
 fi
 if has b256; then
-  timeout 600 python bench.py --per-gpu-batch 256 --steps 20 --warmup 5 --no-cpu-baseline --no-configs4 --gemm-breakdown > "$OUT/bench_b256.json" 2> "$OUT/bench_b256.err"
+  timeout 600 python bench.py --full --per-gpu-batch 256 --steps 20 --warmup 5 --no-cpu-baseline --no-configs4 --gemm-breakdown > "$OUT/bench_b256.json" 2> "$OUT/bench_b256.err"
   echo "b256 exit $?"; tail -c 600 "$OUT/bench_b256.json"
 fi
 if has tri; then
-  timeout 600 python bench.py --tri-modal --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_trimodal_b2048.json" 2> "$OUT/bench_trimodal.err"
+  timeout 600 python bench.py --full --tri-modal --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_trimodal_b2048.json" 2> "$OUT/bench_trimodal.err"
   echo "tri exit $?"; tail -c 600 "$OUT/bench_trimodal_b2048.json"
 fi
 if has fp8; then   # BASELINE configs[4]: opt-in fp8-forward mode — the training-grade selection (mean-pooled towers) and the embedding-grade one (all)
   for tw in pooled all; do
-    timeout 600 python bench.py --fp8-forward $tw --steps 10 --warmup 3 --no-cpu-baseline --no-h2d --gemm-breakdown > "$OUT/bench_fp8_${tw}_b2048.json" 2> "$OUT/bench_fp8_${tw}_b2048.err"
+    timeout 600 python bench.py --full --fp8-forward $tw --steps 10 --warmup 3 --no-cpu-baseline --no-h2d --gemm-breakdown > "$OUT/bench_fp8_${tw}_b2048.json" 2> "$OUT/bench_fp8_${tw}_b2048.err"
     echo "fp8 $tw exit $?"; tail -c 400 "$OUT/bench_fp8_${tw}_b2048.json"
-    timeout 600 python bench.py --fp8-forward $tw --per-gpu-batch 1024 --steps 10 --warmup 3 --no-cpu-baseline --no-h2d > "$OUT/bench_fp8_${tw}_b1024.json" 2> "$OUT/bench_fp8_${tw}_b1024.err"
+    timeout 600 python bench.py --full --fp8-forward $tw --per-gpu-batch 1024 --steps 10 --warmup 3 --no-cpu-baseline --no-h2d > "$OUT/bench_fp8_${tw}_b1024.json" 2> "$OUT/bench_fp8_${tw}_b1024.err"
     echo "fp8 $tw b1024 exit $?"; tail -c 400 "$OUT/bench_fp8_${tw}_b1024.json"
   done
 fi
@@ -67,7 +67,7 @@ if has dram; then   # DRAM share of the L2's memory-side requests per kernel (to
   tail -32 "$OUT/pmc_dram.txt"
 fi
 if has eval; then
-  timeout 900 python bench.py --eval --steps 5 --warmup 2 > "$OUT/bench_eval.json" 2> "$OUT/bench_eval.err"
+  timeout 900 python bench.py --full --eval --steps 5 --warmup 2 > "$OUT/bench_eval.json" 2> "$OUT/bench_eval.err"
   echo "eval exit $?"; tail -c 1800 "$OUT/bench_eval.json"
 fi
 du -sh "$OUT"
