@@ -59,6 +59,7 @@ SIGNATURES = {
     "clibd_gemm_fp8_dgrad_nt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, C.POINTER(GemmEpilogue), c_void_p]),
     "clibd_quantize_rows_fp8_bf16": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "clibd_transpose_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "clibd_transpose_fp8_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
     "clibd_transpose_colsum_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "clibd_transpose_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
     "clibd_transpose_colsum_bf16_ws": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -117,6 +118,10 @@ SIGNATURES = {
     "clibd_layernorm_param_grads": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
     "clibd_gemm_splitk_workspace_bytes": (c_size_t, [c_int, c_int]),
     "clibd_gemm_bf16_tn_splitk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_gemm_fp8b_tn_splitk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                          c_size_t, c_void_p]),
+    "clibd_gemm_fp8b_tn_splitk_ordered": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                                                  c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "clibd_gemm_bf16_nt_splitk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "clibd_dropout_apply_f32": (c_int, [c_void_p, c_size_t, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
     "clibd_batch_sum_f32": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p]),

@@ -13,6 +13,8 @@
 // 64-byte fp32 stores per lane, and full 128-B lines per row across a wave.
 #include <stdlib.h>
 
+#include <cmath>
+
 #include "gemm_common.h"
 #include "host_util.h"
 
@@ -167,6 +169,26 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const unsigned shor
     __syncthreads();
     for (int i = ty; i < 64; i += 4) {
         const int c = c0 + i, r = r0 + tx;   // out row = c, out col = r
+        if (c < C && r < ld_out) out[(size_t)c * ld_out + r] = tile[tx][i];
+    }
+}
+
+// e4m3 -> bf16 transpose with zero padding: out[c, r] = bf16(e4m3(in[r, c]) * scale) (scale = the inverse of the quantisation scale: the
+// transpose + NT fallback of the weight gradient under the fp8 forward).  One byte per thread on the way in, through a padded LDS tile
+__global__ __launch_bounds__(256) void transpose_fp8_bf16_kernel(const unsigned char* __restrict__ in, int ld_in, int R, int C, float scale,
+                                                                 unsigned short* __restrict__ out, int ld_out) {
+    __shared__ unsigned short tile[64][66];
+    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int i = ty; i < 64; i += 4) {
+        const int r = r0 + i, c = c0 + tx;
+        unsigned short v = 0;
+        if (r < R && c < C) v = f2bf(__builtin_amdgcn_cvt_f32_fp8((int)in[(size_t)r * ld_in + c], 0) * scale);
+        tile[i][tx] = v;
+    }
+    __syncthreads();
+    for (int i = ty; i < 64; i += 4) {
+        const int c = c0 + i, r = r0 + tx;
         if (c < C && r < ld_out) out[(size_t)c * ld_out + r] = tile[tx][i];
     }
 }
@@ -569,6 +591,47 @@ extern "C" int clibd_gemm_bf16_tn_splitk_ordered(const void* A, int lda, const v
     return ordered_colsum_launch((const float*)colsum_workspace, splits, Na, colsum_a, Na, nullptr, (hipStream_t)stream);
 }
 
+// full fine-tune under the fp8 forward: the TN weight gradient whose B operand (the layer input X) is the e4m3 image the forward GEMM
+// consumed, dequantised by b_scale in the kernel's fp32 epilogue; same split plan, workspaces and column-sum forms as the bf16 entry points
+static int tn_fp8b_impl(const void* A, int lda, const void* B8, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32, int ld_out,
+                        int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
+                        size_t colsum_workspace_bytes, bool ordered, void* stream) {
+    const char* what = ordered ? "gemm_fp8b_tn_splitk_ordered" : "gemm_fp8b_tn_splitk";
+    if (!A || !B8 || !out_f32 || !workspace || (ordered && (!colsum_a || !colsum_workspace))) return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk: null pointer");
+    if (M <= 0 || Na <= 0 || Nb <= 0 || lda < Na || ldb < Nb || ld_out != Nb || !(b_scale > 0.f) || !std::isfinite(b_scale))
+        return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk: bad shape (out must be dense [Na,Nb]) or b_scale (finite, > 0)");
+    if ((lda & 7) || (ldb & 7) || !aligned16(A) || ((uintptr_t)B8 & 7) || !aligned16(out_f32) || !aligned16(workspace) ||
+        (ordered && !aligned16(colsum_workspace)))
+        return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk: alignment");
+    if (ordered && colsum_workspace_bytes < clibd_gemm_tn_colsum_workspace_bytes(M, Na))
+        return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk_ordered: colsum workspace too small (clibd_gemm_tn_colsum_workspace_bytes)");
+    const int splits = gemm256_tn_fp8b_splitk_launch((const unsigned short*)A, lda, (const unsigned char*)B8, ldb, b_scale, M, Na, Nb, (float*)workspace,
+                                                     workspace_bytes / sizeof(float), colsum_a, (hipStream_t)stream,
+                                                     ordered ? (float*)colsum_workspace : nullptr);
+    if (splits <= 0) return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk: shape not supported (need M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, workspace)");
+    if (int e = check_launch(what)) return e;
+    const size_t n4 = (size_t)Na * Nb / 4;
+    size_t blocks = (n4 + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, splits, n4,
+                       out_f32, accumulate);
+    if (int e = check_launch("reduce_splits")) return e;
+    if (!ordered) return CLIBD_OK;
+    return ordered_colsum_launch((const float*)colsum_workspace, splits, Na, colsum_a, Na, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int clibd_gemm_fp8b_tn_splitk(const void* A, int lda, const void* B8, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32,
+                                         int ld_out, int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* stream) {
+    return tn_fp8b_impl(A, lda, B8, ldb, b_scale, M, Na, Nb, out_f32, ld_out, accumulate, colsum_a, workspace, workspace_bytes, nullptr, 0, false, stream);
+}
+
+extern "C" int clibd_gemm_fp8b_tn_splitk_ordered(const void* A, int lda, const void* B8, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32,
+                                                 int ld_out, int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes,
+                                                 void* colsum_workspace, size_t colsum_workspace_bytes, void* stream) {
+    return tn_fp8b_impl(A, lda, B8, ldb, b_scale, M, Na, Nb, out_f32, ld_out, accumulate, colsum_a, workspace, workspace_bytes, colsum_workspace,
+                        colsum_workspace_bytes, true, stream);
+}
+
 static inline int transpose_row_tile(int ld_out) { return ld_out >= 1024 ? 256 : 64; }
 
 static int transpose_impl(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, void* stream,
@@ -605,6 +668,15 @@ static int transpose_impl(const void* in, int ld_in, int R, int C, void* out, in
 
 extern "C" int clibd_transpose_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, void* stream) {
     return transpose_impl(in, ld_in, R, C, out, ld_out, nullptr, stream);
+}
+
+extern "C" int clibd_transpose_fp8_bf16(const void* in, int ld_in, int R, int C, float scale, void* out, int ld_out, void* stream) {
+    if (!in || !out || R <= 0 || C <= 0 || ld_in < C || ld_out < R || !std::isfinite(scale)) return set_error(CLIBD_EINVAL, "transpose_fp8_bf16: bad args");
+    dim3 grid((C + 63) / 64, (ld_out + 63) / 64);
+    if (grid.y > 65535u) return set_error(CLIBD_EINVAL, "transpose_fp8_bf16: too many rows for one launch");
+    hipLaunchKernelGGL(transpose_fp8_bf16_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned char*)in, ld_in, R, C, scale,
+                       (unsigned short*)out, ld_out);
+    return check_launch("transpose_fp8_bf16");
 }
 
 extern "C" int clibd_transpose_colsum_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, void* stream) {

@@ -26,6 +26,15 @@
 //     (6 %), no extra pass over dY (a separate column-sum kernel cost 7.3 ms per step).  Work items of output-column tile 0
 //     add their slice's sums atomically.
 //
+//   * B8 (fp8 full fine-tune): B is e4m3 with one host dequantisation factor b_scale (dW = dY^T . e4m3(x sa) / sa: the X operand
+//     exactly as the fp8 forward GEMM consumed it).  The LDS image, the transposing fragment reads and the MFMAs are the bf16
+//     kernel's: B's half-tiles are filled through registers instead of LDS-DMA.  At the point where the bf16 kernel issues a B
+//     half-tile's two DMA instructions, each lane issues two 8-byte global loads (the same k-rows, the same vmcnt count) into a
+//     register buffer indexed by (stage, half); four phases later — after the wait that would have covered that DMA — it widens
+//     the 8 bytes to 8 bf16 (exact: every e4m3 value is a bf16 value) and ds_writes them to the chunk position the DMA would have
+//     filled, then waits for its LDS writes before the phase's barrier.  b_scale (a power of two in practice) multiplies the fp32
+//     tile in the epilogue.  The CS column sums are of A and are unaffected.
+//
 // M % 128 == 0, Na % 256 == 0, Nb % 256 == 0, every slice >= 4 K-tiles.
 #include "gemm_common.h"
 #include "host_util.h"
@@ -40,7 +49,7 @@ constexpr int TN_THREADS = 512;
 
 struct TnParams {
     const unsigned short* A;   // [M, lda]  -> output rows
-    const unsigned short* B;   // [M, ldb]  -> output columns
+    const void* B;             // [M, ldb]  -> output columns: bf16, or e4m3 bytes (B8; ldb in elements = bytes)
     int M, Na, Nb, lda, ldb;
     int tiles_a, tiles_b;      // Na / 256, Nb / 256
     int splits, nk_split;      // K-tiles (64 rows) per slice; even, >= 4
@@ -48,13 +57,14 @@ struct TnParams {
     long long split_stride;    // Na * Nb
     float* colsum;             // optional [Na]: += column sums of A (the bias gradient rides along, see CS below)
     float* colsum_partials;    // deterministic mode: [splits][Na], the slice sums stored instead of added atomically (nullptr: atomics)
+    float b_scale;             // B8: the fp32 tile is multiplied by it before it is stored
 };
 
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 
 #define TN_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
-template <bool CS>
+template <bool CS, bool B8>
 __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int nitems) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -66,7 +76,7 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
 
     int a0 = 0, b0 = 0, kb_issue = 0, nk_issue = 0, split_issue = 0;
     bool first_col_tile = false;
-    const unsigned ldA2 = (unsigned)p.lda * 2u, ldB2 = (unsigned)p.ldb * 2u;
+    const unsigned ldA2 = (unsigned)p.lda * 2u, ldB2 = (unsigned)p.ldb * (B8 ? 1u : 2u);   // bytes per row
     const char* const baseA = (const char*)p.A;
     const char* const baseB = (const char*)p.B;
     unsigned offP = 0, offQ = 0;   // per-lane byte offsets inside a chunk's source: k-row (lane>>4)*16, 16-byte piece lane&15
@@ -79,7 +89,8 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
         a0 = ta * 256;
         b0 = tb * 256;
         first_col_tile = tb == 0;
-        offP = (unsigned)(lane >> 4) * 16u * ldB2 + (unsigned)(lane & 15) * 16u + (unsigned)b0 * 2u;
+        if constexpr (B8) offP = (unsigned)(lane >> 4) * 16u * ldB2 + (unsigned)(lane & 15) * 8u + (unsigned)b0;   // 8 e4m3 per lane
+        else offP = (unsigned)(lane >> 4) * 16u * ldB2 + (unsigned)(lane & 15) * 16u + (unsigned)b0 * 2u;
         offQ = (unsigned)(lane >> 4) * 16u * ldA2 + (unsigned)(lane & 15) * 16u + (unsigned)a0 * 2u;
     };
     // this wave fills chunks 2*wave and 2*wave+1 of every half-tile (k-rows n, n+16, n+32, n+48 of the K-tile for chunk n)
@@ -88,17 +99,50 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
     asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\t"                   \
                  "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"                         \
                  :: "v"(off), "s"(sbase0), "s"(sbase1), "s"(ldsdst), "s"((ldsdst) + (unsigned)TN_CHUNK) : "memory", "m0")
+    // B8: the register buffers of B's half-tiles, [stage][half 0 | half 3], two 8-byte pieces (chunks 2 wave, 2 wave + 1) each
+    i32x2 b8buf[2][2][2];
+    // B8: this lane's ds_write position in chunk 2 wave of half 0 (+ stage, half, chunk as immediates: stage 1 takes a base of its own)
+    const unsigned wr8_0 = (unsigned)(size_t)(lds_void*)smem + (unsigned)(2 * wave) * (unsigned)TN_CHUNK + (unsigned)lane * 16u;
+    const unsigned wr8_1 = wr8_0 + (unsigned)TN_STAGE;
+#define TN_GLD8_PAIR(off, sbase0, sbase1, d0, d1)                                                       \
+    asm volatile("global_load_dwordx2 %0, %2, %3\n\tglobal_load_dwordx2 %1, %2, %4"                    \
+                 : "=&v"(d0), "=&v"(d1) : "v"(off), "s"(sbase0), "s"(sbase1) : "memory")
 #define TN_ISSUE(u, j, stage)                                                                           \
     do {                                                                                                \
         const unsigned dst_ = lds_dma0 + (unsigned)((stage) * TN_STAGE + (j) * TN_HALF);                \
         const size_t krow_ = (size_t)(unsigned)((u) + kb_issue) * 64u + (size_t)(2 * wave);             \
         if ((j) == 0 || (j) == 3) {                                                                     \
-            const char* s0_ = baseB + krow_ * ldB2 + ((j) == 3 ? 256 : 0);                              \
-            TN_GLDS_PAIR(offP, s0_, s0_ + ldB2, dst_);                                                  \
+            if constexpr (B8) {                                                                         \
+                const char* s0_ = baseB + krow_ * ldB2 + ((j) == 3 ? 128 : 0);                          \
+                TN_GLD8_PAIR(offP, s0_, s0_ + ldB2, b8buf[(stage)][(j) == 3][0], b8buf[(stage)][(j) == 3][1]); \
+            } else {                                                                                    \
+                const char* s0_ = baseB + krow_ * ldB2 + ((j) == 3 ? 256 : 0);                          \
+                TN_GLDS_PAIR(offP, s0_, s0_ + ldB2, dst_);                                              \
+            }                                                                                           \
         } else {                                                                                        \
             const char* s0_ = baseA + krow_ * ldA2 + ((j) == 2 ? 256 : 0);                              \
             TN_GLDS_PAIR(offQ, s0_, s0_ + ldA2, dst_);                                                  \
         }                                                                                               \
+    } while (0)
+
+    // B8: widen a landed register buffer (8 e4m3 -> 8 bf16 per piece) and ds_write it
+    // where the bf16 kernel's DMA would have put those k-rows; the caller waits for the writes before its barrier
+    // (gfx950's v_cvt_scalef32_pk_bf16_fp8 at scale 1: two e4m3 -> two bf16 per instruction, exact)
+    typedef int i32x4_ __attribute__((ext_vector_type(4)));
+    auto widen8 = [](i32x2 v) {
+        return (i32x4_){__builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[0], 1.0f, false)),
+                        __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[0], 1.0f, true)),
+                        __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[1], 1.0f, false)),
+                        __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v[1], 1.0f, true))};
+    };
+#define TN_WRITE8(stage, j)                                                                             \
+    do {                                                                                                \
+        asm volatile("" : "+v"(b8buf[(stage)][(j) == 3][0]), "+v"(b8buf[(stage)][(j) == 3][1]));        \
+        const auto v0_ = widen8(b8buf[(stage)][(j) == 3][0]);                                            \
+        const auto v1_ = widen8(b8buf[(stage)][(j) == 3][1]);                                            \
+        asm volatile("ds_write_b128 %0, %1 offset:%3\n\tds_write_b128 %0, %2 offset:%4"                 \
+                     :: "v"((stage) ? wr8_1 : wr8_0), "v"(v0_), "v"(v1_), "n"((j) * TN_HALF), "n"((j) * TN_HALF + TN_CHUNK) : "memory"); \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                              \
     } while (0)
 
     // ---- fragment addresses (see header): one VGPR per operand and stage, everything else is an immediate
@@ -172,7 +216,7 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
         __builtin_amdgcn_s_barrier();               \
         asm volatile("" ::: "memory");              \
     } while (0)
-#define TN_PHASE(Q8, issue_ok, WAITN)                                                                        \
+#define TN_PHASE(Q8, issue_ok, WAITN, land_ok)                                                               \
     do {                                                                                                     \
         constexpr int st_ = ((Q8) >> 2) & 1;                                                                 \
         constexpr int dl_ = (Q8) & 3;                                                                        \
@@ -185,6 +229,10 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
             TN_ISSUE(kt + du_, ju_, du_ & 1);                                                                \
         }                                                                                                    \
         TN_WAIT_VMCNT(WAITN);                                                                                \
+        if constexpr (B8) {   /* the half-tile issued four phases ago (same half, other stage) has landed */  \
+            constexpr int jl_ = ((Q8) + 2) & 3;                                                              \
+            if ((land_ok) && (jl_ == 0 || jl_ == 3)) TN_WRITE8(1 - ((((Q8) + 6) >> 2) & 1), jl_);            \
+        }                                                                                                    \
         TN_BARRIER();                                                                                        \
         if (dl_ == 0) { TN_WAIT_W(w0H, w0F); TN_WAIT_A(); }                                                  \
         else if (dl_ == 1) { TN_WAIT_W(w1H, w1F); }                                                          \
@@ -212,6 +260,7 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
         TN_PROLOGUE();
         const int nk = nk_issue;
         TN_WAIT_VMCNT(8);   // L_0 .. L_3 of this item have landed (this wave's pieces)
+        if constexpr (B8) { TN_WRITE8(0, 0); TN_WRITE8(0, 3); }
         TN_BARRIER();
         if (wm == 1) TN_BARRIER();   // stagger: group 1 runs one barrier interval behind group 0
 #pragma unroll
@@ -229,16 +278,18 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
                 for (int d = 0; d < 2; ++d) csum[c][d] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
         int kt = 0;   // nk >= 4, even (host-checked)
-        TN_PHASE(0, false, 8); TN_PHASE(1, false, 8);   // L_6, L_7 were part of the prologue
-        TN_PHASE(2, true, 8); TN_PHASE(3, true, 8); TN_PHASE(4, true, 8); TN_PHASE(5, true, 8); TN_PHASE(6, true, 8); TN_PHASE(7, true, 8);
+        // (land_ok, B8: a half-tile issued four phases earlier has just landed — in phases 0, 1 of the first iteration that is tile 0,
+        // written above, and in phases 6, 7 of the last nothing was issued four phases earlier)
+        TN_PHASE(0, false, 8, false); TN_PHASE(1, false, 8, false);   // L_6, L_7 were part of the prologue
+        TN_PHASE(2, true, 8, true); TN_PHASE(3, true, 8, true); TN_PHASE(4, true, 8, true); TN_PHASE(5, true, 8, true); TN_PHASE(6, true, 8, true); TN_PHASE(7, true, 8, true);
         for (kt = 2; kt < nk - 2; kt += 2) {
-            TN_PHASE(0, true, 8); TN_PHASE(1, true, 8); TN_PHASE(2, true, 8); TN_PHASE(3, true, 8);
-            TN_PHASE(4, true, 8); TN_PHASE(5, true, 8); TN_PHASE(6, true, 8); TN_PHASE(7, true, 8);
+            TN_PHASE(0, true, 8, true); TN_PHASE(1, true, 8, true); TN_PHASE(2, true, 8, true); TN_PHASE(3, true, 8, true);
+            TN_PHASE(4, true, 8, true); TN_PHASE(5, true, 8, true); TN_PHASE(6, true, 8, true); TN_PHASE(7, true, 8, true);
         }
         // last iteration (kt = nk - 2): two half-tiles left to issue, then drain with exact counts
-        TN_PHASE(0, true, 8); TN_PHASE(1, true, 8);
-        TN_PHASE(2, false, 6); TN_PHASE(3, false, 4);
-        TN_PHASE(4, false, 2); TN_PHASE(5, false, 0); TN_PHASE(6, false, 0); TN_PHASE(7, false, 0);
+        TN_PHASE(0, true, 8, true); TN_PHASE(1, true, 8, true);
+        TN_PHASE(2, false, 6, true); TN_PHASE(3, false, 4, true);
+        TN_PHASE(4, false, 2, true); TN_PHASE(5, false, 0, true); TN_PHASE(6, false, 0, false); TN_PHASE(7, false, 0, false);
         if (wm == 0) TN_BARRIER();   // group 0 matches group 1's extra barrier; every LDS read of this item is complete
 
         // ---- epilogue: lane (c = lane&15, g) holds output rows a0 + 128 hn + 32 wn + 16 n + 4 g + r, column b0 + 128 hm + 64 wm + 16 t + c
@@ -258,7 +309,7 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
 #pragma unroll
                         for (int hm = 0; hm < 2; ++hm)
 #pragma unroll
-                            for (int t = 0; t < 4; ++t) orow[128 * hm + 16 * t] = acc[hm][t][hn][n][r];
+                            for (int t = 0; t < 4; ++t) orow[128 * hm + 16 * t] = B8 ? acc[hm][t][hn][n][r] * p.b_scale : acc[hm][t][hn][n][r];
                     }
             if constexpr (CS) {
                 if (first_col_tile && wm == 0 && ec == 0) {
@@ -279,9 +330,9 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
     }
 }
 
-// Returns the number of M-slices used (>= 1) or 0 when the shape is not one this kernel takes.
-int gemm256_tn_splitk_launch(const unsigned short* A, int lda, const unsigned short* B, int ldb, int M, int Na, int Nb, float* partials,
-                             size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials) {
+// Returns the number of M-slices used (>= 1) or 0 when the shape is not one this kernel takes.  b_scale > 0: B is e4m3 (B8).
+static int tn_splitk_launch(const unsigned short* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* partials,
+                            size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials, float b_scale) {
     if (M <= 0 || M % 128 != 0 || Na % 256 != 0 || Nb % 256 != 0 || Na <= 0 || Nb <= 0) return 0;
     const int nk = M / 64;
     if (nk < 4) return 0;
@@ -307,15 +358,31 @@ int gemm256_tn_splitk_launch(const unsigned short* A, int lda, const unsigned sh
     q.split_stride = (long long)Na * Nb;
     q.colsum = colsum;
     q.colsum_partials = colsum != nullptr ? colsum_partials : nullptr;
-    static const bool attr_ok = hipFuncSetAttribute((const void*)gemm256_tn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS) == hipSuccess &&
-                                hipFuncSetAttribute((const void*)gemm256_tn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS) == hipSuccess;
+    q.b_scale = b_scale;
+    const bool b8 = b_scale > 0.f;
+    static const bool attr_ok = hipFuncSetAttribute((const void*)gemm256_tn_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS) == hipSuccess &&
+                                hipFuncSetAttribute((const void*)gemm256_tn_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS) == hipSuccess &&
+                                hipFuncSetAttribute((const void*)gemm256_tn_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS) == hipSuccess &&
+                                hipFuncSetAttribute((const void*)gemm256_tn_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS) == hipSuccess;
     if (!attr_ok) return 0;
     int nitems = tiles * splits;
     const int grid = nitems < num_cus ? nitems : num_cus;
     void* args[] = {(void*)&q, (void*)&nitems};
-    const void* fn = colsum != nullptr ? (const void*)gemm256_tn_kernel<true> : (const void*)gemm256_tn_kernel<false>;
+    const void* fn = colsum != nullptr ? (b8 ? (const void*)gemm256_tn_kernel<true, true> : (const void*)gemm256_tn_kernel<true, false>)
+                                       : (b8 ? (const void*)gemm256_tn_kernel<false, true> : (const void*)gemm256_tn_kernel<false, false>);
     if (hipLaunchKernel(fn, dim3((unsigned)grid), dim3(TN_THREADS), args, TN_LDS, stream) != hipSuccess) return 0;
     return splits;
+}
+
+int gemm256_tn_splitk_launch(const unsigned short* A, int lda, const unsigned short* B, int ldb, int M, int Na, int Nb, float* partials,
+                             size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials) {
+    return tn_splitk_launch(A, lda, B, ldb, M, Na, Nb, partials, partials_elems, colsum, stream, colsum_partials, 0.f);
+}
+
+int gemm256_tn_fp8b_splitk_launch(const unsigned short* A, int lda, const unsigned char* B8, int ldb, float b_scale, int M, int Na, int Nb,
+                                  float* partials, size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials) {
+    if (!(b_scale > 0.f)) return 0;
+    return tn_splitk_launch(A, lda, B8, ldb, M, Na, Nb, partials, partials_elems, colsum, stream, colsum_partials, b_scale);
 }
 
 }  // namespace clibd

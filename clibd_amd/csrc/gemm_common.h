@@ -578,5 +578,8 @@ int gemm256_splitk_launch(const GemmParams& p, float* partials, size_t partials_
 // returns the number of slices (0: shape not taken)
 int gemm256_tn_splitk_launch(const unsigned short* A, int lda, const unsigned short* B, int ldb, int M, int Na, int Nb, float* partials,
                              size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials = nullptr);
+// the same with B as e4m3 bytes (ldb in bytes) and the tile multiplied by b_scale (> 0) before it is stored
+int gemm256_tn_fp8b_splitk_launch(const unsigned short* A, int lda, const unsigned char* B8, int ldb, float b_scale, int M, int Na, int Nb,
+                                  float* partials, size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials = nullptr);
 
 }  // namespace clibd

@@ -248,10 +248,15 @@ class TransformerStack:
           * otherwise the static `scales` / FP8_SCALES for every layer (fits unit-variance LayerNorm outputs, random-init or
             lightly trained towers; pretrained checkpoints with outlier channels want the calibration).
         The backward is unchanged bf16 (it needs gelu', qkv, statistics and — for the adapters — the bf16 LayerNorm output
-        only): gradients are those of the bf16 network evaluated at the fp8 forward's activations.  LoRA / frozen-base mode only.
+        only): gradients are those of the bf16 network evaluated at the fp8 forward's activations.
         sites (round 5): a subset of FP8_SITES — ("fc1_in", "fc2_in") runs the MLP of every block on the fp8 MFMA
         and leaves QKV, attention and the projection on bf16 operands (the per-layer dicts then hold those sites only, which is also
-        how the oracle is told: a site without a scale is a bf16 site).  The oracle study behind it: profiles/r05_exp_fp8_vit_sites.log."""
+        how the oracle is told: a site without a scale is a bf16 site).  The oracle study behind it: profiles/r05_exp_fp8_vit_sites.log.
+        Trainable base weights (full fine-tune, full_mode()): the MLP-pair selection only.  The weight gradients of fc1 and fc2 contract
+        the e4m3 operands the forward GEMMs consumed, dW = dY^T . e4m3(x sa) / sa (ops.gemm_tn_splitk with an e4m3 b: exact upcast, the
+        power-of-two 1 / sa in the fp32 epilogue), so the rule above holds for them too; the e4m3 weight images are re-made from the
+        fp32 masters at every refresh (every step under full fine-tune).  The all-site selection stays LoRA / frozen-base only
+        (embedding-grade)."""
         if sites is not None:
             sites = tuple(sites)
             if any(s not in self.FP8_SITES for s in sites):
@@ -259,8 +264,9 @@ class TransformerStack:
             if set(sites) != set(self.FP8_SITES):
                 if set(sites) != {"fc1_in", "fc2_in"}:
                     raise NotSupportedYet("fp8 site selection: only the MLP pair (fc1_in, fc2_in) is built")
-        if self.full_mode():
-            raise NotSupportedYet("fp8 forward needs frozen base weights (their gradients would need the bf16 GEMM inputs)")
+        if self.full_mode() and (sites is None or set(sites) != {"fc1_in", "fc2_in"}):
+            raise NotSupportedYet("fp8 forward on every site needs frozen base weights (their gradients would need the bf16 GEMM inputs); "
+                                  "with trainable base weights the MLP-pair selection (sites=('fc1_in', 'fc2_in')) is built")
         if self.H % 256 or self.H < 512 or self.FF % 256:
             raise NotSupportedYet("fp8 forward needs hidden % 256 == 0, hidden >= 512, intermediate % 256 == 0")
         base = dict(self.FP8_SCALES, **(scales or {}))
@@ -426,7 +432,8 @@ class TransformerStack:
         the last block are dead code the reference computes and discards).
         drop (post-LN only): (p_hidden, p_attention, base_seed) — HF BERT train-mode dropout; site seeds via ops.derive_seed.
         full: full fine-tune mode — every layer keeps its own attention output, MLP input and GELU output (the X operands of
-        the weight gradients) instead of sharing temporaries.
+        the weight gradients) instead of sharing temporaries; under the fp8 MLP-pair selection the MLP input and GELU output are the
+        e4m3 images the fp8 GEMMs consumed, recorded with their scales (xn2_s / x1_s, a_s).
         x_fp8 (post-LN, fp8-forward mode): the e4m3 image of x (scale fp8[0]["qkv_in"]) from the embedding LayerNorm."""
         H, FF, M = self.H, self.FF, B * S
         dev = x_f32.device
@@ -434,13 +441,13 @@ class TransformerStack:
         new = lambda cols, dt: torch.empty((M, cols), dtype=dt, device=dev)
         keep = save and full
         f8s = self.fp8
-        if f8s is not None and full:
-            raise NotSupportedYet("fp8 forward with trainable base weights")
+        mlp_only = f8s is not None and "qkv_in" not in f8s[0]   # fp8 site selection: QKV / attention / projection stay bf16
+        if f8s is not None and full and not mlp_only:
+            raise NotSupportedYet("fp8 forward on every site with trainable base weights (the MLP-pair selection is built)")
         cal = self._calib if f8s is None else None      # calibration pass: bf16 forward recording max |operand| per site
         amax = lambda t_: t_.abs().amax().float()
         f8 = None
         AT = ops.FP8 if f8s is not None else BF16    # dtype of the GEMM-operand temporaries
-        mlp_only = f8s is not None and "qkv_in" not in f8s[0]   # fp8 site selection: QKV / attention / projection stay bf16
         o = None if keep else new(H, BF16 if mlp_only else AT)   # attention output (temporary, reused by every layer)
         a = None if keep else new(FF, AT)           # post-GELU activation (temporary)
         xn2 = new(H, AT) if (self.pre_ln and not keep) else None
@@ -469,9 +476,9 @@ class TransformerStack:
             t2 = None   # further rank slots' down-projections (LoRA ranks above 4): a list
             f8 = f8s[i] if f8s is not None else None
             crec = {} if cal is not None else None
-            if keep:
-                o, a = new(H, BF16), new(FF, BF16)
-                xn2 = new(H, BF16) if self.pre_ln else None
+            if keep:   # (fp8 MLP pair: the MLP's operands are the e4m3 images the weight gradients contract)
+                o, a = new(H, BF16), new(FF, AT)
+                xn2 = new(H, AT) if self.pre_ln else None
             if self.pre_ln and cls_only_last and i == len(self.layers) - 1:
                 xn = new(H, BF16)
                 st1 = torch.empty((M, 2), dtype=F32, device=dev)
@@ -561,6 +568,8 @@ class TransformerStack:
                     rec = dict(x_in=x_f32, st1=st1, xn=xn, t=t, t2=t2, qkv=qkv, x1=x1, st2=st2, h=h)
                     if keep:
                         rec.update(o=o, xn2=xn2, a=a)
+                        if f8 is not None:
+                            rec.update(xn2_s=f8["fc1_in"], a_s=f8["fc2_in"])
                     if att_sv is not None:
                         rec.update(att_sv)
                 x_f32 = x2
@@ -629,6 +638,8 @@ class TransformerStack:
                                d_att=d_att, d_h1=d_h1, d_h2=d_h2)
                     if keep:
                         rec.update(o=o, x1_bf16=x1_bf16, a=a)
+                        if f8 is not None:
+                            rec.update(x1_bf16=x18, x1_s=f8["fc1_in"], a_s=f8["fc2_in"])
                     if att_sv is not None:
                         rec.update(att_sv)
                 x_f32, x_bf16, t = x2_f32, x2_bf16, t_next
@@ -677,7 +688,8 @@ class TransformerStack:
         det = self.deterministic
         pg = lambda w, b: (dict(dgamma=grads[id(w)].view(-1), dbeta=grads[id(b)].view(-1), **_ordered(det))
                            if full and id(w) in grads else {})
-        wg = lambda dy, x, ws, bs: linear_wgrad(dy, x, ws, bs, grads, **_ordered(det)) if full else None
+        # (fp8 forward, MLP pair: rec holds the e4m3 GEMM inputs and their scales — xn2_s / x1_s, a_s — and linear_wgrad contracts those)
+        wg = lambda dy, x, ws, bs, xs=None: linear_wgrad(dy, x, ws, bs, grads, x_scale=xs, **_ordered(det)) if full else None
         for i in range(len(self.layers) - 1, -1, -1):
             L, c, rec = self.layers[i], self._cache[i], saved[i]
             has_lora = L.lora is not None
@@ -717,19 +729,19 @@ class TransformerStack:
                         ops.layernorm_bwd(dtmp, rec["x_in"], rec["st1"], c.g1, dres=dres_full, dx_f32=ndx_f32, dx_bf16=ndx_bf16, **pg(L.ln1_w, L.ln1_b))
                         dx_f32, dx_bf16 = ndx_f32, ndx_bf16
             elif self.pre_ln:
-                wg(dx_bf16, rec.get("a"), [L.fc2_w], [L.fc2_b])
+                wg(dx_bf16, rec.get("a"), [L.fc2_w], [L.fc2_b], rec.get("a_s"))
                 if dg8 and dx8 is not None:   # d(fc1 out) leaves as e4m3 with the rows' scales x c2; the fc1 dgrad divides both back out
                     dh8 = torch.empty((M, FF), dtype=torch.uint8, device=dev).view(ops.FP8)
                     if full:   # ... and once more as bf16: the operand of fc1's weight gradient
                         dh = new(FF, BF16) if dh is None else dh
                     ops.gemm_fp8_dgrad_nt(dx8[0], c.w2_t8, c.cs_2t, aux=rec["h"], act=_mul_aux_act(rec["h"], FF), out_fp8=dh8, out_fp8_scale=c.c2,
                                           a_row_dequant=dx8[1] if full else None, out_bf16_dual=dh if full else None)
-                    wg(dh, rec.get("xn2"), [L.fc1_w], [L.fc1_b])
+                    wg(dh, rec.get("xn2"), [L.fc1_w], [L.fc1_b], rec.get("xn2_s"))
                     ops.gemm_fp8_dgrad_nt(dh8, c.w1_t8, c.cs_1t, a_row_dequant=dx8[1], out_bf16=dtmp)
                 else:
                     dh = new(FF, BF16) if dh is None else dh
                     ops.gemm_nt(dx_bf16, c.w2_t, act=_mul_aux_act(rec["h"], FF), aux=rec["h"], out_bf16=dh)      # d(fc1 out)
-                    wg(dh, rec.get("xn2"), [L.fc1_w], [L.fc1_b])
+                    wg(dh, rec.get("xn2"), [L.fc1_w], [L.fc1_b], rec.get("xn2_s"))
                     ops.gemm_nt(dh, c.w1_t, out_bf16=dtmp)                                               # d(LN2 out)
                 dx18 = new8(H) if (dg8 and "proj" in self.dgrad8_sites) else None
                 if r16:
@@ -788,17 +800,17 @@ class TransformerStack:
                 if dg8:
                     dh8 = torch.empty((M, FF), dtype=torch.uint8, device=dev).view(ops.FP8)
                     if full:
-                        wg(ds2_b, rec.get("a"), [L.fc2_w], [L.fc2_b])
+                        wg(ds2_b, rec.get("a"), [L.fc2_w], [L.fc2_b], rec.get("a_s"))
                         dh = new(FF, BF16) if dh is None else dh
                     ops.gemm_fp8_dgrad_nt(ds2_8[0], c.w2_t8, c.cs_2t, aux=rec["h"], act=_mul_aux_act(rec["h"], FF), out_fp8=dh8, out_fp8_scale=c.c2,
                                           a_row_dequant=ds2_8[1] if full else None, out_bf16_dual=dh if full else None)
-                    wg(dh, rec.get("x1_bf16"), [L.fc1_w], [L.fc1_b])
+                    wg(dh, rec.get("x1_bf16"), [L.fc1_w], [L.fc1_b], rec.get("x1_s"))
                     ops.gemm_fp8_dgrad_nt(dh8, c.w1_t8, c.cs_1t, a_row_dequant=ds2_8[1], aux=ds2_res, act=ops.ACT_ADD_AUX, out_bf16=dx1)
                 else:
                     dh = new(FF, BF16) if dh is None else dh
-                    wg(ds2_b, rec.get("a"), [L.fc2_w], [L.fc2_b])
+                    wg(ds2_b, rec.get("a"), [L.fc2_w], [L.fc2_b], rec.get("a_s"))
                     ops.gemm_nt(ds2_b, c.w2_t, act=_mul_aux_act(rec["h"], FF), aux=rec["h"], out_bf16=dh)
-                    wg(dh, rec.get("x1_bf16"), [L.fc1_w], [L.fc1_b])
+                    wg(dh, rec.get("x1_bf16"), [L.fc1_w], [L.fc1_b], rec.get("x1_s"))
                     ops.gemm_nt(dh, c.w1_t, act=ops.ACT_ADD_AUX, aux=ds2_res, out_bf16=dx1)
                 ds1_res, ds1_b, ds1_8 = ln_back(dx1, rec["s1"], rec["st1"], c.g1, rec["d_h1"], pg(L.ln1_w, L.ln1_b))
                 if dg8:
@@ -825,10 +837,10 @@ class TransformerStack:
             else:
                 ds2_f32, ds2_bf16 = new(H, F32), new(H, BF16)
                 ops.layernorm_bwd(dx_f32, rec["s2"], rec["st2"], c.g2, dx_f32=ds2_f32, dx_bf16=ds2_bf16, drop=rec["d_h2"], **pg(L.ln2_w, L.ln2_b))
-                wg(ds2_bf16, rec.get("a"), [L.fc2_w], [L.fc2_b])
+                wg(ds2_bf16, rec.get("a"), [L.fc2_w], [L.fc2_b], rec.get("a_s"))
                 dh = new(FF, BF16) if dh is None else dh
                 ops.gemm_nt(ds2_bf16, c.w2_t, act=_mul_aux_act(rec["h"], FF), aux=rec["h"], out_bf16=dh)
-                wg(dh, rec.get("x1_bf16"), [L.fc1_w], [L.fc1_b])
+                wg(dh, rec.get("x1_bf16"), [L.fc1_w], [L.fc1_b], rec.get("x1_s"))
                 dx1 = new(H, F32)
                 ops.gemm_nt(dh, c.w1_t, residual=ds2_f32, out_f32=dx1)
                 ds1_f32, ds1_bf16 = new(H, F32), new(H, BF16)
@@ -887,17 +899,23 @@ class TransformerStack:
 
 
 def linear_wgrad(dy_bf16: torch.Tensor, x_bf16: torch.Tensor, weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], grads: dict,
-                 ordered: bool = False):
+                 ordered: bool = False, x_scale: Optional[float] = None):
     """Weight / bias gradients of y = x W^T + b for the parameters present in `grads` (accumulating):
     dW [N,K] += dy^T x — read in place by the rows-contracting kernel when the shape allows (M % 128 == 0, N and K % 256 == 0:
     every full-size layer), else as the NT GEMM (dy^T [N,Mp]) (x^T [K,Mp])^T over zero-padded transposes —
     db += column sums of dy.  `weights` may be the row-wise pieces of a fused projection (BERT query / key / value).
     ordered (deterministic mode): every sum in a fixed order — the TN form's bias sums per slice, the generic GEMM unsplit (its split-K form
-    accumulates atomically), the column-sum kernel through partials."""
+    accumulates atomically), the column-sum kernel through partials.
+    x as float8_e4m3fn (fp8 forward): the GEMM input as the forward consumed it, e4m3(x * x_scale); dW += dy^T (x8 / x_scale) — the
+    rows-contracting kernel's e4m3 form, or the transpose + NT path over a dequantising transpose (both exact upcasts)."""
     if not any(id(w) in grads for w in weights) and not any(id(b) in grads for b in biases):
         return
     if x_bf16 is None:
         raise RuntimeError("full fine-tune backward needs the layer's GEMM input (forward ran without full=True)")
+    x8 = x_bf16.dtype == ops.FP8
+    if x8 and (x_scale is None or not x_scale > 0.0):
+        raise ValueError("linear_wgrad: an e4m3 input needs its quantisation scale (x_scale > 0)")
+    tn_kw = dict(b_scale=1.0 / x_scale) if x8 else {}
     M = dy_bf16.shape[0]
     want_b = [b is not None and id(b) in grads for b in biases]
     bias_done = False
@@ -915,7 +933,8 @@ def linear_wgrad(dy_bf16: torch.Tensor, x_bf16: torch.Tensor, weights: Sequence[
             took = False
             if pending[j]:
                 cs = grads[id(b)].view(-1) if wb else None
-                took = ops.gemm_tn_splitk(dy_bf16[:, n0:n1], x_bf16, grads[id(w)].view(w.shape[0], -1), accumulate=True, colsum=cs, **_ordered(ordered))
+                took = ops.gemm_tn_splitk(dy_bf16[:, n0:n1], x_bf16, grads[id(w)].view(w.shape[0], -1), accumulate=True, colsum=cs, **_ordered(ordered),
+                                          **tn_kw)
                 pending[j] = not took
             done.append(took and wb)
             n0 = n1
@@ -929,7 +948,7 @@ def linear_wgrad(dy_bf16: torch.Tensor, x_bf16: torch.Tensor, weights: Sequence[
             else:
                 csum = torch.zeros((N,), dtype=F32, device=dy_bf16.device)   # column sums of dy in the same pass as its transpose
         dyT = ops.transpose_bf16(dy_bf16, pad_to=128, colsum=csum)   # [N, Mp]
-        xT = ops.transpose_bf16(x_bf16, pad_to=128)     # [K, Mp]
+        xT = ops.transpose_fp8(x_bf16, 1.0 / x_scale, pad_to=128) if x8 else ops.transpose_bf16(x_bf16, pad_to=128)     # [K, Mp]
         Mp = dyT.shape[1]
         split = 1 if ordered else max(1, min(32, Mp // 2048))
         n0 = 0

@@ -130,7 +130,9 @@ class SimpleCLIP(nn.Module):
     def enable_fp8_forward(self, scales: Optional[dict] = None, enabled: bool = True, calibration_inputs=None, margin: float = 2.0,
                            towers=None):
         """fp8-forward mode (BASELINE.json configs[4]; not in the reference, which trains under bf16 autocast): the selected towers'
-        forward GEMMs run on the fp8 MFMA, see TransformerStack.enable_fp8.  Needs frozen base weights (LoRA mode).
+        forward GEMMs run on the fp8 MFMA, see TransformerStack.enable_fp8.  With trainable base weights (full fine-tune) the MLP-pair
+        selections only: "pooled_ffn" (and any tower the selection gives the pair, e.g. the ViT of "pooled_mlp"); a tower on all four
+        sites ("pooled", "all", the mean-pooled towers of "pooled_mlp") needs frozen base weights and raises NotSupportedYet.
         towers: "pooled" (default: the mean-pooled towers, training-grade), "all" (adds the ViT: embedding-grade), or an iterable of
         encoder attribute names; None keeps the previous selection (what Trainer's periodic re-calibration passes).
         calibration_inputs = (image_input, dna_input, language_input): one bf16 no-grad forward over that batch measures

@@ -6,6 +6,7 @@ operands on the host, takes raw pointers and enqueues hand-written gfx950 kernel
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
@@ -384,6 +385,18 @@ def transpose_bf16(x: torch.Tensor, pad_to: int = 64, colsum: Optional[torch.Ten
               "transpose_colsum_bf16_ws")
     else:
         check(_lib.load().clibd_transpose_bf16(x.data_ptr(), ld, R, Cc, out.data_ptr(), Rp, _stream()), "transpose_bf16")
+    return out
+
+
+def transpose_fp8(x: torch.Tensor, scale: float, pad_to: int = 64) -> torch.Tensor:
+    """[R,C] float8_e4m3fn -> [C, R_pad] bf16 holding x * scale (zero padded along R to a multiple of `pad_to`): the transposed,
+    dequantised X operand of a weight gradient under the fp8 forward (scale = 1 / the quantisation scale; a power of two is exact)."""
+    _chk(x, FP8, "x", contiguous=False)
+    ld = _rowmajor(x, "x")
+    R, Cc = x.shape
+    Rp = (R + pad_to - 1) // pad_to * pad_to
+    out = torch.empty((Cc, Rp), dtype=BF16, device=x.device)
+    check(_lib.load().clibd_transpose_fp8_bf16(x.data_ptr(), ld, R, Cc, float(scale), out.data_ptr(), Rp, _stream()), "transpose_fp8_bf16")
     return out
 
 
@@ -1074,11 +1087,22 @@ _splitk_ws = {}
 
 
 def gemm_tn_splitk(a: torch.Tensor, b: torch.Tensor, out_f32: torch.Tensor, accumulate: bool = True, colsum: Optional[torch.Tensor] = None,
-                   ordered: bool = False) -> bool:
+                   ordered: bool = False, b_scale: Optional[float] = None) -> bool:
     """out[Na,Nb] (+)= a[M,Na]^T @ b[M,Nb], both operands read in place (clibd_gemm_bf16_tn_splitk): the weight gradient
     dW = dy^T x without transposes; colsum (fp32 [Na]) += column sums of a in the same pass (the bias gradient).
-    Returns False (nothing launched) when the shape is outside the kernel's.  ordered: the column sums per M-slice, summed in slice order."""
-    _chk(a, BF16, "a", contiguous=False); _chk(b, BF16, "b", contiguous=False); _chk(out_f32, F32, "out_f32")
+    Returns False (nothing launched) when the shape is outside the kernel's.  ordered: the column sums per M-slice, summed in slice order.
+    b as float8_e4m3fn with b_scale (> 0; required): out (+)= a^T @ (b * b_scale) (clibd_gemm_fp8b_tn_splitk) — the weight gradient of a
+    GEMM whose forward consumed x as e4m3(x * sa), with b_scale = 1 / sa."""
+    b8 = b.dtype == FP8
+    if b8:
+        if b_scale is None or not (float(b_scale) > 0.0) or not math.isfinite(float(b_scale)):
+            raise ValueError("gemm_tn_splitk: an e4m3 b needs b_scale > 0 (finite)")
+        _chk(b, FP8, "b", contiguous=False)
+    elif b_scale is not None:
+        raise ValueError("gemm_tn_splitk: b_scale goes with an e4m3 b only")
+    else:
+        _chk(b, BF16, "b", contiguous=False)
+    _chk(a, BF16, "a", contiguous=False); _chk(out_f32, F32, "out_f32")
     M, Na = a.shape
     Nb = b.shape[1]
     if b.shape[0] != M or tuple(out_f32.shape) != (Na, Nb):
@@ -1096,6 +1120,19 @@ def gemm_tn_splitk(a: torch.Tensor, b: torch.Tensor, out_f32: torch.Tensor, accu
         _chk(colsum, F32, "colsum")
         if colsum.numel() != Na:
             raise ValueError("gemm_tn_splitk: colsum must have Na elements")
+    if b8:
+        if ordered and colsum is not None:
+            cws = _ordered_workspace("tn_colsum", int(lib.clibd_gemm_tn_colsum_workspace_bytes(M, Na)), a.device)
+            rc = lib.clibd_gemm_fp8b_tn_splitk_ordered(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), float(b_scale), M, Na, Nb,
+                                                       out_f32.data_ptr(), Nb, int(accumulate), colsum.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                                       cws.data_ptr(), cws.numel(), _stream())
+        else:
+            rc = lib.clibd_gemm_fp8b_tn_splitk(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), float(b_scale), M, Na, Nb,
+                                               out_f32.data_ptr(), Nb, int(accumulate), _p(colsum), ws.data_ptr(), ws.numel() * 4, _stream())
+        if rc != 0 and b"shape not supported" in (lib.clibd_last_error() or b""):
+            return False
+        check(rc, "gemm_fp8b_tn_splitk")
+        return True
     if ordered and colsum is not None:
         cws = _ordered_workspace("tn_colsum", int(lib.clibd_gemm_tn_colsum_workspace_bytes(M, Na)), a.device)
         rc = lib.clibd_gemm_bf16_tn_splitk_ordered(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), M, Na, Nb, out_f32.data_ptr(), Nb,

@@ -163,6 +163,9 @@ int clibd_quantize_rows_fp8_bf16(const void* w_bf16, int N, int K, float act_sca
 /* bf16 transpose with zero padding: out[C, ld_out] (ld_out >= R) = in[R, C]^T; columns R..ld_out-1 zero.
  * Used to feed the weight-gradient GEMMs (contraction over the token dimension). */
 int clibd_transpose_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, void* stream);
+/* out[c, r] = bf16(e4m3(in[r, c]) * scale), rows R .. ld_out-1 of out zero (in: OCP e4m3 bytes [R, ld_in]; ABI 5, additive): the
+ * transposed, dequantised X operand of the fp8-forward weight gradient where the rows-contracting kernel does not take the shape. */
+int clibd_transpose_fp8_bf16(const void* in, int ld_in, int R, int C, float scale, void* out, int ld_out, void* stream);
 /* same, and colsum[c] += sum_r in[r, c] (fp32, accumulates): the bias gradient of a linear layer rides along with the transpose
  * of dy that its weight gradient needs (full fine-tune mode).  Needs C, ld_in, ld_out multiples of 8, 16-byte aligned bases. */
 int clibd_transpose_colsum_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, void* stream);
@@ -445,6 +448,14 @@ int clibd_gemm_bf16_nt_splitk(const void* A, int lda, const void* W, int ldw, in
  * M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, lda / ldb % 8 == 0; workspace >= clibd_gemm_splitk_workspace_bytes(Na, Nb). */
 int clibd_gemm_bf16_tn_splitk(const void* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* out_f32, int ld_out,
                               int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* stream);
+/* The same product with B as OCP e4m3 bytes and one dequantisation factor: out[Na,Nb] (+)= A[M,Na]^T · (B8[M,Nb] * b_scale) (ABI 5,
+ * additive).  The weight gradient of a linear layer whose forward GEMM consumed its input as e4m3(x sa) (fp8 forward under full
+ * fine-tune): dW = dY^T · e4m3(x sa) / sa with b_scale = 1 / sa.  The e4m3 values are widened to bf16 exactly and b_scale multiplies
+ * the fp32 tile, so for a power-of-two b_scale the result equals clibd_gemm_bf16_tn_splitk on bf16(B8 * b_scale) bit for bit.  Same
+ * shapes, split plan, workspace and colsum_a as that entry point; ldb (in elements = bytes) % 8 == 0, B8 8-byte aligned, b_scale > 0.
+ * The _ordered form matches clibd_gemm_bf16_tn_splitk_ordered (declared below with the deterministic mode). */
+int clibd_gemm_fp8b_tn_splitk(const void* A, int lda, const void* B8, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32,
+                              int ld_out, int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- full fine-tune mode (model_config.disable_lora): parameter gradients that are not GEMM-shaped.
  * Every output ACCUMULATES (atomicAdd) into fp32 buffers the caller zeroes once per step.
@@ -495,6 +506,10 @@ size_t clibd_gemm_tn_colsum_workspace_bytes(int M, int Na);
 int clibd_gemm_bf16_tn_splitk_ordered(const void* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* out_f32, int ld_out,
                                       int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
                                       size_t colsum_workspace_bytes, void* stream);
+/* clibd_gemm_fp8b_tn_splitk with colsum_a (required) stored per M-slice and summed in slice order. */
+int clibd_gemm_fp8b_tn_splitk_ordered(const void* A, int lda, const void* B8, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32,
+                                      int ld_out, int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes,
+                                      void* colsum_workspace, size_t colsum_workspace_bytes, void* stream);
 
 /* fused AdamW step on a flat fp32 parameter bucket (torch.optim.AdamW semantics, scripts/train_cl.py:221):
  * p,g,m,v [n]; g is multiplied by grad_scale first (1/world_size folding etc.). */
