@@ -166,3 +166,304 @@ def make_prediction(query_feature, keys_feature, keys_label: List[dict], with_si
     if with_indices:
         out.append(idx_h)
     return out[0] if len(out) == 1 else out
+
+
+# ================================================================================================================================
+# The eval phase (reference scripts/train_cl.py:73-86,124-143 and bioscanclip/util/util.py:379-395,555-742): every query type x key
+# type x {seen, unseen} search scored on the device (clibd_topk_label_hits); only integer counts come back to the host, where the
+# reference's float64 arithmetic is restated exactly.
+QUERY_FEATURE_TYPES = ["encoded_image_feature", "encoded_dna_feature", "encoded_language_feature", "averaged_feature", "concatenated_feature"]
+KEY_FEATURE_TYPES = QUERY_FEATURE_TYPES + ["all_key_features"]
+
+
+class LabelCodec:
+    """Per level, one dict mapping every label seen so far (keys first, then queries) to a dense int32 id.  Labels must be hashable
+    and equal by `==` (as `gt_label in pred_labels` compares them); NaN labels are unsupported."""
+
+    def __init__(self, levels: Sequence[str] = LEVELS):
+        self.levels = list(levels)
+        self.maps = [dict() for _ in self.levels]
+
+    def encode(self, label_list: Sequence[dict]) -> np.ndarray:
+        """int32 [N, L] ids of a list of {level: label}; labels not seen before get the next free id of their level."""
+        out = np.empty((len(label_list), len(self.levels)), dtype=np.int32)
+        for l, level in enumerate(self.levels):
+            m = self.maps[l]
+            out[:, l] = [m.setdefault(d[level], len(m)) for d in label_list]
+        return out
+
+    def labels(self, l: int) -> list:
+        """The labels of level l in id order."""
+        return list(self.maps[l])
+
+    def _table(self, l: int) -> np.ndarray:
+        t = np.empty(len(self.maps[l]), dtype=object)    # (filled one by one: tuple labels must stay single objects)
+        for i, lab in enumerate(self.maps[l]):
+            t[i] = lab
+        return t
+
+    def decode(self, ids: np.ndarray) -> List[dict]:
+        """int [N, L] ids -> [{level: label}] (the inverse of `encode`)."""
+        ids = np.asarray(ids)
+        per_level = [self._table(l)[ids[:, l]].tolist() for l in range(len(self.levels))]
+        return [dict(zip(self.levels, row)) for row in zip(*per_level)]
+
+    def decode_rows(self, key_ids: np.ndarray, idx: np.ndarray) -> List[dict]:
+        """[{level: [labels of the keys idx[q, :]]}] per query, the reference's make_prediction lists; key_ids int [Nk, L]."""
+        per_level = [self._table(l)[key_ids[idx, l]].tolist() for l in range(len(self.levels))]
+        return [dict(zip(self.levels, row)) for row in zip(*per_level)]
+
+    def class_offset(self) -> List[int]:
+        """[0, n_0, n_0 + n_1, ...]: the per-level class axes flattened into one (clibd_topk_label_hits' class_offset)."""
+        off = [0]
+        for m in self.maps:
+            off.append(off[-1] + len(m))
+        return off
+
+
+# Key-side label ids, next to the key-bank cache: an eval phase searches the same key labels with every query type.  Label LISTS are
+# matched by identity (the entry holds the list, so its id cannot be reused); a list mutated in place is not detected.
+_label_cache: dict = {}
+_LABEL_CACHE_ENTRIES = 4
+
+
+def _cached_key_label_ids(keys_label: list, device):
+    key = (id(keys_label), str(device))
+    hit = _label_cache.get(key)
+    if hit is not None and hit[0] is keys_label and hit[1] == len(keys_label):
+        return hit[2], hit[3]
+    codec = LabelCodec()
+    ids = torch.from_numpy(codec.encode(keys_label)).to(device)
+    if len(_label_cache) >= _LABEL_CACHE_ENTRIES:
+        _label_cache.pop(next(iter(_label_cache)))
+    _label_cache[key] = (keys_label, len(keys_label), codec, ids)
+    return codec, ids
+
+
+def clear_eval_caches() -> None:
+    """Drop the cached key bank and the cached key-label ids."""
+    clear_key_bank_cache()
+    _label_cache.clear()
+
+
+def _check_k_list(k_list) -> List[int]:
+    ks = [int(k) for k in k_list]
+    if not ks or any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 1 or ks[-1] > 8:
+        raise ValueError(f"k_list must be strictly ascending with 1 <= k <= 8, got {list(k_list)}")
+    return ks
+
+
+def _split_accuracy(level_hits: np.ndarray, class_hits: np.ndarray, class_count: np.ndarray, query_ids: np.ndarray, codec: LabelCodec,
+                    offset: Sequence[int], k_list: Sequence[int], k_rows: Sequence[int]):
+    """Integer counts of one query split -> (micro, macro, per_class) in the reference's float64 arithmetic (util.py:379-395,555-599):
+      micro[k][level] = hits * 1.0 / Q;
+      per_class[k][level][label] = hits_c * 1.0 / count_c over the split's ground-truth labels in order of first appearance;
+      macro[k][level] = a sequential left-to-right float64 sum of those, divided by their number (np.cumsum adds in order; np.sum
+      would add pairwise and differ in the last bits).
+    level_hits [n_k', L], class_hits [n_k', C], class_count [C]; k_rows[i]: the row of k_list[i]."""
+    Q = query_ids.shape[0]
+    micro, macro, per_class = {}, {}, {}
+    order, names = [], []
+    for l in range(len(codec.levels)):
+        u, first = np.unique(query_ids[:, l], return_index=True)
+        ids = u[np.argsort(first, kind="stable")]
+        order.append(offset[l] + ids.astype(np.int64))
+        lab = codec.labels(l)
+        names.append([lab[i] for i in ids.tolist()])
+    for k, j in zip(k_list, k_rows):
+        micro[k], macro[k], per_class[k] = {}, {}, {}
+        for l, level in enumerate(codec.levels):
+            micro[k][level] = int(level_hits[j, l]) * 1.0 / Q
+            vals = class_hits[j, order[l]].astype(np.float64) / class_count[order[l]].astype(np.float64)
+            macro[k][level] = float(np.cumsum(vals)[-1]) / len(vals)
+            per_class[k][level] = dict(zip(names[l], vals.tolist()))
+    return micro, macro, per_class
+
+
+def _as_device(x, device) -> torch.Tensor:
+    if torch.is_tensor(x):
+        return x.detach().to(device=device, dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)
+
+
+def _score_prediction_lists(pred_list, gt_list, k_list):
+    """The reference's list-of-dicts convention on the hits kernel: the predicted labels become a small key table [Q * m, L] and
+    the indices are the identity (row q of the search = keys q*m .. q*m + m - 1)."""
+    ks = _check_k_list([1, 3, 5] if k_list is None else k_list)
+    Q = len(pred_list)
+    if Q == 0 or len(gt_list) != Q:
+        raise ValueError("top-k accuracy: need as many ground-truth labels as predictions, and at least one")
+    lens = {len(p[level]) for p in pred_list for level in LEVELS}
+    if len(lens) != 1 or 0 in lens:
+        raise ValueError("top-k accuracy: every prediction list must have the same, non-zero length")
+    m = min(lens.pop(), ks[-1])
+    kk = sorted({min(k, m) for k in ks})           # pred[level][:k] with k beyond the list is the whole list
+    codec = LabelCodec()
+    keys = np.empty((Q * m, len(LEVELS)), dtype=np.int32)
+    for l, level in enumerate(LEVELS):
+        mp = codec.maps[l]
+        keys[:, l] = [mp.setdefault(lab, len(mp)) for p in pred_list for lab in p[level][:m]]
+    gt = codec.encode(gt_list)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    idx = torch.from_numpy(np.arange(Q * m, dtype=np.int64).reshape(Q, m)).to(dev)
+    off = codec.class_offset()
+    _, lh, ch, cc = ops.topk_label_hits(idx, torch.from_numpy(keys).to(dev), torch.from_numpy(gt).to(dev), off, kk)
+    lh, ch, cc = lh.cpu().numpy()[0], ch.cpu().numpy()[0], cc.cpu().numpy()[0]
+    return _split_accuracy(lh, ch, cc, gt, codec, off, ks, [kk.index(min(k, m)) for k in ks])
+
+
+def top_k_micro_accuracy(pred_list, gt_list, k_list=None):
+    """{k: {level: fraction of queries whose label is among the first k predicted}} (reference util.py:379-395), counted on the GPU."""
+    return _score_prediction_lists(pred_list, gt_list, k_list)[0]
+
+
+def top_k_macro_accuracy(pred_list, gt_list, k_list=None):
+    """({k: {level: mean per-class accuracy}}, {k: {level: {label: accuracy}}}) (reference util.py:555-599), counted on the GPU."""
+    _, macro, per_class = _score_prediction_lists(pred_list, gt_list, k_list)
+    return macro, per_class
+
+
+def get_features_and_label(dataloader, model, device, for_key_set=False, for_open_clip=False, as_numpy=True):
+    """The reference's per-split dictionary (util.py:702-742): the three embeddings of `get_feature_and_label`, their average and
+    concatenation (clibd_eval_pair_features; fp32, unnormalised as the reference stores them) and, for a key set with all three
+    towers, `all_key_features` = image | dna | text keys with the labels repeated three times.  as_numpy=False keeps every
+    feature a device tensor."""
+    file_name_list, img, dna, text, label_list = get_feature_and_label(dataloader, model, device, for_open_clip=for_open_clip, as_numpy=False)
+    averaged = concatenated = all_keys = all_keys_label = None
+    if img is not None and dna is not None:
+        averaged, concatenated = ops.eval_pair_features(img, dna)
+    if for_key_set and img is not None and dna is not None and text is not None:
+        all_keys = torch.cat([img, dna, text], dim=0)
+        all_keys_label = label_list + label_list + label_list
+    conv = (lambda t: None if t is None else t.cpu().numpy()) if as_numpy else (lambda t: t)
+    return {
+        "file_name_list": file_name_list,
+        "encoded_dna_feature": conv(dna),
+        "encoded_image_feature": conv(img),
+        "encoded_language_feature": conv(text),
+        "averaged_feature": conv(averaged),
+        "concatenated_feature": conv(concatenated),
+        "label_list": label_list,
+        "all_key_features": conv(all_keys),
+        "all_key_features_label": all_keys_label,
+    }
+
+
+def _print_acc_table(acc_dict, k_list) -> None:
+    head = ["query -> key", "acc", "k"] + [f"{s} {lv}" for s in ("seen", "unseen") for lv in LEVELS]
+    print(" | ".join(head))
+    for qt, per_key in acc_dict.items():
+        for kt, per_split in per_key.items():
+            if not per_split:
+                continue
+            for kind in ("micro_acc", "macro_acc"):
+                for k in k_list:
+                    vals = [f"{per_split[s][kind][k][lv]:.4f}" for s in ("seen", "unseen") for lv in LEVELS]
+                    print(" | ".join([f"{qt} -> {kt}", kind, str(k)] + vals))
+
+
+def inference_and_print_result(keys_dict, seen_dict, unseen_dict, args=None, small_species_list=None, k_list=None, with_predictions=True):
+    """The reference's inference_and_print_result (util.py:601-700): the same loop order over query type x key type, the same
+    skip rules (absent or None features, a feature width that differs from the keys'; `all_key_features` searched with its own
+    labels) and the same return triple (acc_dict, per_class_acc, pred_dict).
+
+    Per key type the keys are prepared once (one bank for the pre-filtered search at >= 4 096 keys) and re-used by every query
+    type; the seen and unseen queries go through ONE search and ONE clibd_topk_label_hits launch (segment 0 / 1).  Only integer
+    counts (and, for pred_dict, the index arrays) come back to the host.  with_predictions=False stores the int64 index arrays
+    [Q, max_k] in pred_dict instead of the reference's per-query label lists.  Prints a plain table (the reference's CSV output and
+    `args` header are not reproduced).  Stated divergence: fewer keys than max(k_list) is a ValueError (faiss returns -1 there)."""
+    k_list = _check_k_list([1, 3, 5] if k_list is None else k_list)
+    max_k = k_list[-1]
+    seen_gt, unseen_gt = seen_dict["label_list"], unseen_dict["label_list"]
+    keys_label = keys_dict["label_list"]
+    if "processed_id_list" in seen_dict and "processed_id_list" in unseen_dict:
+        pred_dict = {"seen_id": seen_dict["processed_id_list"], "seen_gt_label": seen_gt,
+                     "unseen_id": unseen_dict["processed_id_list"], "unseen_gt_label": unseen_gt}
+    else:
+        pred_dict = {"seen_id": seen_dict.get("file_name_list", []), "seen_gt_label": seen_gt,
+                     "unseen_id": unseen_dict.get("file_name_list", []), "unseen_gt_label": unseen_gt}
+    tensors = [v for d in (keys_dict, seen_dict, unseen_dict) for v in d.values() if torch.is_tensor(v) and v.is_cuda]
+    dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
+    Qs, Qu = len(seen_gt), len(unseen_gt)
+    segment = torch.from_numpy(np.repeat(np.array([0, 1], dtype=np.int32), [Qs, Qu])).to(dev)
+    prepared = {}     # key type -> KeyBank (pre-filtered search) or device keys (exact search), shared by every query type
+    encoded = {}      # id(codec) -> (device ids of seen | unseen, host ids of seen, host ids of unseen)
+    acc_dict, per_class_acc = {}, {}
+    for qt in QUERY_FEATURE_TYPES:
+        if qt not in seen_dict:
+            continue
+        acc_dict[qt], per_class_acc[qt], pred_dict[qt] = {}, {}, {}
+        queries = None
+        for kt in KEY_FEATURE_TYPES:
+            if kt not in keys_dict:
+                continue
+            acc_dict[qt][kt], per_class_acc[qt][kt], pred_dict[qt][kt] = {}, {}, {}
+            sf, uf, kf = seen_dict[qt], unseen_dict[qt], keys_dict[kt]
+            if kf is None:
+                continue
+            if kt == "all_key_features":
+                keys_label = keys_dict["all_key_features_label"]   # (and kept for the key types after it, as in the reference)
+            if sf is None or uf is None or kf.shape[-1] != sf.shape[-1] or kf.shape[-1] != uf.shape[-1]:
+                continue
+            Nk, D = kf.shape
+            if Nk < max_k:
+                raise ValueError(f"{kt}: {Nk} keys cannot fill a top-{max_k} search")
+            if kt not in prepared:
+                keys = _as_device(kf, dev)
+                eligible = D % 64 == 0 and D <= ops.KeyBank.MAX_D and 4096 <= Nk < ops.KeyBank.MAX_KEYS
+                prepared[kt] = prepare_key_bank(keys) if eligible else keys
+            if queries is None:
+                queries = torch.cat([_as_device(sf, dev), _as_device(uf, dev)], dim=0)
+            codec, key_ids = _cached_key_label_ids(keys_label, dev)
+            if id(codec) not in encoded:
+                s_ids, u_ids = codec.encode(seen_gt), codec.encode(unseen_gt)
+                encoded[id(codec)] = (torch.from_numpy(np.concatenate([s_ids, u_ids])).to(dev), s_ids, u_ids)
+            q_ids, s_ids, u_ids = encoded[id(codec)]
+            _, idx = topk_search(queries, prepared[kt], max_k, cache=False)
+            off = codec.class_offset()
+            _, lh, ch, cc = ops.topk_label_hits(idx, key_ids, q_ids, off, k_list, segment=segment, nseg=2)
+            lh, ch, cc = lh.cpu().numpy(), ch.cpu().numpy(), cc.cpu().numpy()
+            rows = list(range(len(k_list)))
+            s_micro, s_macro, s_per_class = _split_accuracy(lh[0], ch[0], cc[0], s_ids, codec, off, k_list, rows)
+            u_micro, u_macro, u_per_class = _split_accuracy(lh[1], ch[1], cc[1], u_ids, codec, off, k_list, rows)
+            idx_h = idx.cpu().numpy()
+            if with_predictions:
+                key_ids_h = key_ids.cpu().numpy()
+                pred_dict[qt][kt] = {"curr_seen_pred_list": codec.decode_rows(key_ids_h, idx_h[:Qs]),
+                                     "curr_unseen_pred_list": codec.decode_rows(key_ids_h, idx_h[Qs:])}
+            else:
+                pred_dict[qt][kt] = {"curr_seen_pred_list": idx_h[:Qs], "curr_unseen_pred_list": idx_h[Qs:]}
+            acc_dict[qt][kt]["seen"] = {"micro_acc": s_micro, "macro_acc": s_macro}
+            acc_dict[qt][kt]["unseen"] = {"micro_acc": u_micro, "macro_acc": u_macro}
+            per_class_acc[qt][kt]["seen"] = s_per_class
+            per_class_acc[qt][kt]["unseen"] = u_per_class
+    _print_acc_table(acc_dict, k_list)
+    return acc_dict, per_class_acc, pred_dict
+
+
+def eval_phase(model, device, all_keys_dataloader, seen_val_dataloader, unseen_val_dataloader, k_list, args=None, species_to_drop=None, rank=None,
+               for_open_clip=False, with_predictions=True):
+    """The reference's eval_phase (scripts/train_cl.py:73-86): key, seen and unseen features, then every search scored.
+    Features stay on the device between the two steps.  Returns (acc_dict, pred_dict)."""
+    if for_open_clip:
+        raise NotImplementedError("open_clip towers are out of scope (DESIGN §8)")
+    keys_dict = get_features_and_label(all_keys_dataloader, model, device, for_key_set=True, as_numpy=False)
+    seen_dict = get_features_and_label(seen_val_dataloader, model, device, as_numpy=False)
+    unseen_dict = get_features_and_label(unseen_val_dataloader, model, device, as_numpy=False)
+    acc_dict, _, pred_dict = inference_and_print_result(keys_dict, seen_dict, unseen_dict, args=args, k_list=k_list, with_predictions=with_predictions)
+    return acc_dict, pred_dict
+
+
+def compute_overall_acc(acc_dict) -> float:
+    """The checkpoint-selection number of scripts/train_cl.py:124-143: the mean of every accuracy in acc_dict except those at
+    k = 3 and k = 5, summed left to right in acc_dict's order."""
+    vals = []
+    for per_key in acc_dict.values():
+        for per_split in per_key.values():
+            for per_kind in per_split.values():
+                for table in per_kind.values():
+                    for k, per_level in table.items():
+                        if k == 3 or k == 5:
+                            continue
+                        vals.extend(per_level.values())
+    return sum(vals) / len(vals)

@@ -998,6 +998,63 @@ def kmer_tokenize(seq_u8: torch.Tensor, k: int = 5) -> torch.Tensor:
     return out
 
 
+def topk_label_hits(idx: torch.Tensor, key_labels: torch.Tensor, query_labels: torch.Tensor, class_offset, k_list, segment: Optional[torch.Tensor] = None,
+                    nseg: int = 1):
+    """clibd_topk_label_hits: score a finished search against per-level class ids.  idx int64 [Q, kmax] (a search's output),
+    key_labels int32 [Nk, L], query_labels int32 [Q, L], class_offset: L + 1 ints (host), k_list: strictly ascending ints <= kmax,
+    segment: optional int32 [Q] in [0, nseg).  Returns (first_hit [Q, L], level_hits [nseg, n_k, L], class_hits [nseg, n_k, C],
+    class_count [nseg, C]), int32 device tensors.  Reads one error word back (a host sync): an index outside [0, Nk), a query label
+    outside its level's range or a segment outside [0, nseg) raises ValueError."""
+    _chk(idx, I64, "idx")
+    _chk(key_labels, I32, "key_labels")
+    _chk(query_labels, I32, "query_labels")
+    if idx.dim() != 2 or key_labels.dim() != 2 or query_labels.dim() != 2:
+        raise ValueError("topk_label_hits: idx, key_labels and query_labels must be 2-D")
+    Q, kmax = idx.shape
+    Nk, L = key_labels.shape
+    if tuple(query_labels.shape) != (Q, L):
+        raise ValueError(f"topk_label_hits: query_labels must be [{Q}, {L}], got {list(query_labels.shape)}")
+    off = (C.c_int32 * (L + 1))(*[int(v) for v in class_offset]) if len(class_offset) == L + 1 else None
+    if off is None:
+        raise ValueError(f"topk_label_hits: class_offset needs L + 1 = {L + 1} entries")
+    ks = (C.c_int32 * len(k_list))(*[int(k) for k in k_list])
+    if segment is not None:
+        _chk(segment, I32, "segment")
+        if tuple(segment.shape) != (Q,):
+            raise ValueError("topk_label_hits: segment must be [Q]")
+    n_k, Ccls = len(k_list), int(class_offset[-1])
+    dev = idx.device
+    first_hit = torch.empty((Q, L), dtype=I32, device=dev)
+    level_hits = torch.empty((nseg, n_k, L), dtype=I32, device=dev)
+    class_hits = torch.empty((nseg, n_k, max(Ccls, 1)), dtype=I32, device=dev)
+    class_count = torch.empty((nseg, max(Ccls, 1)), dtype=I32, device=dev)
+    err = torch.empty((1,), dtype=I32, device=dev)
+    lib = _lib.load()
+    check(lib.clibd_topk_label_hits(idx.data_ptr(), Q, kmax, key_labels.data_ptr(), Nk, query_labels.data_ptr(), L, off, ks, n_k, _p(segment), nseg,
+                                    first_hit.data_ptr(), level_hits.data_ptr(), class_hits.data_ptr(), class_count.data_ptr(), err.data_ptr(),
+                                    _stream()), "topk_label_hits")
+    e = int(err.item())
+    if e:
+        what = [m for b, m in ((1, "a key index outside [0, Nk)"), (2, "a query label outside its level's class range"), (4, "a segment outside [0, nseg)"))
+                if e & b]
+        raise ValueError(f"topk_label_hits: {', '.join(what)}")
+    return first_hit, level_hits, class_hits, class_count
+
+
+def eval_pair_features(img: torch.Tensor, dna: torch.Tensor):
+    """clibd_eval_pair_features: (averaged fp32 [N, D], concatenated fp32 [N, 2D]) of two embeddings, as the reference's
+    get_features_and_label builds them (np.mean([img, dna], 0) rounded to fp32, np.concatenate((img, dna), 1)); unnormalised."""
+    _chk(img, F32, "img")
+    _chk(dna, F32, "dna")
+    if img.dim() != 2 or img.shape != dna.shape:
+        raise ValueError("eval_pair_features: img and dna must be 2-D of one shape")
+    N, D = img.shape
+    avg = torch.empty((N, D), dtype=F32, device=img.device)
+    cat = torch.empty((N, 2 * D), dtype=F32, device=img.device)
+    check(_lib.load().clibd_eval_pair_features(img.data_ptr(), dna.data_ptr(), N, D, avg.data_ptr(), cat.data_ptr(), _stream()), "eval_pair_features")
+    return avg, cat
+
+
 # ------------------------------------------------------------------------------------------------ full fine-tune mode (f4)
 def layernorm_param_grads(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, dgamma: torch.Tensor, dbeta: torch.Tensor,
                           drop: Optional[Drop] = None, ordered: bool = False) -> None:

@@ -433,6 +433,27 @@ int clibd_topk_ip_fast(const float* q, const float* keys, const void* keys_bf16,
  * (A0 C1 G2 T3, product('ACGT', repeat=k) order) or 2 (<UNK>) for a k-mer with any other character. */
 int clibd_kmer_tokenize(const void* seq_u8, int B, int L, int k, int64_t* out, void* stream);
 
+/* Eval phase (additive to ABI 5): scores a finished search against labels (reference util/util.py:379-395,555-700, the
+ * top_k_micro_accuracy / top_k_macro_accuracy loops of inference_and_print_result).
+ * idx int64 [Q, kmax] (device; as clibd_topk_ip / clibd_topk_ip_fast write it), key_labels int32 [Nk, L], query_labels int32 [Q, L]
+ * (device; per-level class ids, query ids in [0, class_offset[l+1] - class_offset[l])).  HOST arrays: class_offset int32 [L + 1]
+ * (class_offset[0] = 0, non-decreasing; C = class_offset[L] flattens the per-level class axes) and k_list int32 [n_k] (strictly
+ * ascending, 1 <= k <= kmax <= 8, n_k <= 8).  segment: optional int32 [Q] in [0, nseg) (NULL: nseg must be 1), e.g. 0 = seen,
+ * 1 = unseen, so one launch scores several query splits.  Outputs (device int32, zeroed by the call):
+ *   first_hit [Q, L]          first rank r < kmax whose key label equals the query's, kmax if none (labels compared, not indices)
+ *   level_hits [nseg, n_k, L] queries with first_hit < k
+ *   class_hits [nseg, n_k, C] the same per query class (c = class_offset[l] + query label)
+ *   class_count [nseg, C]     queries per class
+ *   error [1]                 bit 0: an index outside [0, Nk); bit 1: a query label outside its level's range; bit 2: a segment outside
+ *                             [0, nseg).  Offending entries are never dereferenced (nor counted); the caller checks the word once.
+ * Integer atomics only, aggregated per wave: the counts are exact and identical from run to run. */
+int clibd_topk_label_hits(const int64_t* idx, int Q, int kmax, const int32_t* key_labels, int Nk, const int32_t* query_labels, int L,
+                          const int32_t* class_offset, const int32_t* k_list, int n_k, const int32_t* segment, int nseg,
+                          int32_t* first_hit, int32_t* level_hits, int32_t* class_hits, int32_t* class_count, int32_t* error, void* stream);
+/* The reference's averaged_feature (np.mean([img, dna], 0), rounded to fp32) and concatenated_feature ([img | dna]) of two
+ * embeddings in one pass: img, dna fp32 [N, D] -> avg fp32 [N, D], cat fp32 [N, 2D].  D % 4 == 0, 16-byte aligned. */
+int clibd_eval_pair_features(const float* img, const float* dna, int N, int D, float* avg, float* cat, void* stream);
+
 /* Split-K GEMM through a partials workspace: out[M,N] (fp32, dense, ld_out == N) = (accumulate ? out : 0) + A[M,K] . W[N,K]^T.
  * For products with few output tiles and a very long contraction — the weight gradients dW = dY^T X of the full
  * fine-tune mode (autograd of every nn.Linear on the path), A = dY^T [N_w, tokens], W = X^T [K_w, tokens].
