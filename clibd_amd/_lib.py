@@ -118,6 +118,8 @@ SIGNATURES = {
     "clibd_topk_label_hits": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "clibd_eval_pair_features": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "clibd_image_transform_workspace_bytes": (c_size_t, [c_int]),
+    "clibd_image_transform_u8": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "clibd_layernorm_param_grads": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
     "clibd_gemm_splitk_workspace_bytes": (c_size_t, [c_int, c_int]),
     "clibd_gemm_bf16_tn_splitk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -9,7 +9,7 @@ from typing import List, Sequence
 import numpy as np
 import torch
 
-from . import ops
+from . import augment, ops
 
 LEVELS = ["order", "family", "genus", "species"]
 
@@ -32,7 +32,8 @@ def get_feature_and_label(dataloader, model, device, for_open_clip=False, multi_
     every batch runs the towers under no_grad, the second `F.normalize` of the reference (:87-92) is the L2-norm kernel, and
     the embeddings stay on the device until ONE copy at the end.
 
-    Batches are the reference's 7-tuples (processid, image, dna, input_ids, token_type_ids, attention_mask, label dict);
+    Batches are the reference's 7-tuples (processid, image, dna, input_ids, token_type_ids, attention_mask, label dict); `image` may be
+    a packed batch of decoded pixels with eval records (clibd_amd.augment.collate_encoded(..., train=False));
     `dna` may be a tensor of token ids or a list of raw barcode strings (tokenised by the 5-mer kernel; the remote
     BarcodeBERT tokenizer of the newer checkpoints is out of scope, SURVEY §8a-a5').
     Returns (file_name_list, image_features, dna_features, text_features, label_list) like the reference — features as
@@ -57,7 +58,9 @@ def get_feature_and_label(dataloader, model, device, for_open_clip=False, multi_
                     dna_input_batch = dna_input_batch.to(dev)
                 elif getattr(model, "dna_encoder", None) is not None:
                     dna_input_batch = tokenize_barcodes(list(dna_input_batch), dev)
-                image_in = image_input_batch.to(dev) if getattr(model, "image_encoder", None) is not None else None
+                image_in = None
+                if getattr(model, "image_encoder", None) is not None:   # packed decoded pixels: the eval transform on the device
+                    image_in = augment.apply(image_input_batch, dev) if augment.is_packed(image_input_batch) else image_input_batch.to(dev)
                 outs = model(image_in, dna_input_batch, language_input)[:3]
                 for store, out in zip(feats, outs):
                     if out is not None:

@@ -998,6 +998,27 @@ def kmer_tokenize(seq_u8: torch.Tensor, k: int = 5) -> torch.Tensor:
     return out
 
 
+def image_transform(data: torch.Tensor, xforms: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Packed RGB HWC uint8 pixels `data` [N] + per-image records `xforms` int32 [B, 18] (struct clibd_image_xform; built by
+    clibd_amd.augment) -> fp32 [B,3,224,224]: the dataset's Resize / crop / flip / rotation chain (clibd_image_transform_u8).
+    The records are validated on the host when they are built; the kernel reads no byte outside `data` whatever they hold."""
+    _chk(data, torch.uint8, "data")
+    _chk(xforms, I32, "xforms")
+    if data.dim() != 1 or data.numel() == 0:
+        raise ValueError("image_transform: data must be a non-empty 1-D uint8 tensor")
+    if xforms.dim() != 2 or xforms.shape[1] != 18 or xforms.shape[0] == 0 or xforms.device != data.device:
+        raise ValueError("image_transform: xforms must be int32 [B, 18] on the data's device")
+    B = xforms.shape[0]
+    lib = _lib.load()
+    need = int(lib.clibd_image_transform_workspace_bytes(B))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=data.device)
+    out = torch.empty((B, 3, 224, 224), dtype=F32, device=data.device)
+    check(lib.clibd_image_transform_u8(data.data_ptr(), data.numel(), xforms.data_ptr(), B, out.data_ptr(), workspace.data_ptr(),
+                                       workspace.numel(), _stream()), "image_transform_u8")
+    return out
+
+
 def topk_label_hits(idx: torch.Tensor, key_labels: torch.Tensor, query_labels: torch.Tensor, class_offset, k_list, segment: Optional[torch.Tensor] = None,
                     nseg: int = 1):
     """clibd_topk_label_hits: score a finished search against per-level class ids.  idx int64 [Q, kmax] (a search's output),

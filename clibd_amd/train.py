@@ -11,6 +11,7 @@ from typing import Optional
 
 import torch
 
+from . import augment
 from .model.loss_func import ClipLoss, ContrastiveLoss, collectives_forced
 from .optim import FusedAdamW
 
@@ -196,7 +197,8 @@ class Trainer:
 
 
 def train_epoch(total_epochs, epoch, dataloader, trainer: Trainer, device, scheduler=None, log_every: int = 0):
-    """Epoch loop over the reference's 7-tuple batches (util/dataset.py:294-302)."""
+    """Epoch loop over the reference's 7-tuple batches (util/dataset.py:294-302).  An image entry that is a packed batch of decoded
+    pixels (clibd_amd.augment.collate_encoded) goes through the training transform on the device first."""
     trainer.model.train()
     running = torch.zeros((), device=device)
     n = 0
@@ -205,7 +207,8 @@ def train_epoch(total_epochs, epoch, dataloader, trainer: Trainer, device, sched
         text = None
         if trainer.model.language_encoder is not None:
             text = {"input_ids": input_ids.to(device), "token_type_ids": token_type_ids.to(device), "attention_mask": attention_mask.to(device)}
-        loss = trainer.step(image.to(device), dna.to(device), text, label.to(device))
+        image = augment.apply(image, device) if augment.is_packed(image) else image.to(device)
+        loss = trainer.step(image, dna.to(device), text, label.to(device))
         if scheduler is not None:
             scheduler.step()
         running += loss

@@ -454,6 +454,33 @@ int clibd_topk_label_hits(const int64_t* idx, int Q, int kmax, const int32_t* ke
  * embeddings in one pass: img, dna fp32 [N, D] -> avg fp32 [N, D], cat fp32 [N, 2D].  D % 4 == 0, 16-byte aligned. */
 int clibd_eval_pair_features(const float* img, const float* dna, int N, int D, float* avg, float* cat, void* stream);
 
+/* f1 batch contract, images (additive to ABI 5): the dataset's transforms on the device, from the decoded pixels to the model's input
+ * (util/dataset.py:185-195 training: ToTensor -> Resize(256, antialias) -> RandomResizedCrop(224, antialias) -> RandomHorizontalFlip ->
+ * RandomVerticalFlip -> RandomRotation((-45, 45)); :216-224 eval: ToTensor -> Resize(256, antialias) -> CenterCrop(224)).
+ * data: the images' RGB HWC uint8 pixels packed at each record's byte offset (sizes may differ within a batch), data_bytes long.
+ * xforms: one DEVICE record per image (8-byte aligned), parameters drawn and validated on the host (clibd_amd/augment.py).
+ * out_f32 [B,3,224,224] (16-byte aligned): value = fp32(u8) / 255 (IEEE division), resampled in fp32 with torch's separable antialiased
+ * bilinear filter: Resize H0 x W0 -> H1 x W1 (taps clamped to the image), then the box (top, left, h, w) of that image -> 224 x 224 (taps
+ * clamped to the box; the eval CenterCrop is a box of 224 x 224, i.e. a copy), the flags' flips (horizontal, then vertical), then with
+ * CLIBD_XF_ROTATE the rotation of torchvision F.rotate(NEAREST, fill 0) by theta (the fp32 inverse affine matrix
+ * [cos a, -sin a, 0, sin a, cos a, 0] of the angle a in radians).
+ * A record outside the limits (h, w <= 384; H0 <= 16 H1, W0 <= 16 W1; the pixels inside [0, data_bytes)) yields a zero image: no record
+ * makes a kernel read outside the buffers.  workspace: clibd_image_transform_workspace_bytes(B) bytes, 16-byte aligned.  No atomics: a
+ * launch repeats bit for bit and an image's output does not depend on the rest of the batch. */
+enum { CLIBD_XF_HFLIP = 1, CLIBD_XF_VFLIP = 2, CLIBD_XF_ROTATE = 4 };
+typedef struct clibd_image_xform {
+    int64_t offset;             /* byte offset of the image's pixels in data */
+    int32_t H0, W0;             /* decoded size */
+    int32_t H1, W1;             /* size after Resize(256) (== H0, W0: no resize) */
+    int32_t top, left, h, w;    /* crop box in the H1 x W1 image, resampled to 224 x 224 */
+    int32_t flags;              /* CLIBD_XF_* */
+    int32_t reserved;           /* 0 */
+    float theta[6];
+} clibd_image_xform;            /* 72 bytes */
+size_t clibd_image_transform_workspace_bytes(int B);
+int clibd_image_transform_u8(const void* data, size_t data_bytes, const clibd_image_xform* xforms, int B, float* out_f32, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* Split-K GEMM through a partials workspace: out[M,N] (fp32, dense, ld_out == N) = (accumulate ? out : 0) + A[M,K] . W[N,K]^T.
  * For products with few output tiles and a very long contraction — the weight gradients dW = dY^T X of the full
  * fine-tune mode (autograd of every nn.Linear on the path), A = dY^T [N_w, tokens], W = X^T [K_w, tokens].
