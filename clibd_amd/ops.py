@@ -1076,6 +1076,71 @@ def eval_pair_features(img: torch.Tensor, dna: torch.Tensor):
     return avg, cat
 
 
+def threshold_sweep_hits(conf: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, key_labels_a: torch.Tensor, key_labels_b: torch.Tensor,
+                         query_labels: torch.Tensor, thresholds: torch.Tensor, k_list, segment: Optional[torch.Tensor] = None, nseg: int = 1):
+    """clibd_threshold_sweep_hits: top-k label hits of the merged prediction (A's key where (double)conf > t, else B's) at EVERY threshold.
+    conf fp32 [Q, m], idx_a / idx_b int64 [Q, m], key_labels_a int32 [Nka, L], key_labels_b int32 [Nkb, L], query_labels int32 [Q, L],
+    thresholds fp64 [T] (device), k_list: strictly ascending ints <= m, segment: optional int32 [Q] in [0, nseg).  Returns level_hits
+    int32 [T, nseg, n_k, L] (device).  Reads one error word back (a host sync): an index outside its key table, a negative query label
+    or a segment outside [0, nseg) raises ValueError."""
+    _chk(conf, F32, "conf")
+    _chk(idx_a, I64, "idx_a")
+    _chk(idx_b, I64, "idx_b")
+    _chk(key_labels_a, I32, "key_labels_a")
+    _chk(key_labels_b, I32, "key_labels_b")
+    _chk(query_labels, I32, "query_labels")
+    _chk(thresholds, torch.float64, "thresholds")
+    if conf.dim() != 2 or idx_a.shape != conf.shape or idx_b.shape != conf.shape:
+        raise ValueError("threshold_sweep_hits: conf, idx_a and idx_b must be 2-D of one shape")
+    if key_labels_a.dim() != 2 or key_labels_b.dim() != 2 or query_labels.dim() != 2 or thresholds.dim() != 1:
+        raise ValueError("threshold_sweep_hits: label tables must be 2-D and thresholds 1-D")
+    Q, m = conf.shape
+    Nka, L = key_labels_a.shape
+    Nkb = key_labels_b.shape[0]
+    if key_labels_b.shape[1] != L or tuple(query_labels.shape) != (Q, L):
+        raise ValueError(f"threshold_sweep_hits: key_labels_b must be [Nkb, {L}] and query_labels [{Q}, {L}]")
+    if segment is not None:
+        _chk(segment, I32, "segment")
+        if tuple(segment.shape) != (Q,):
+            raise ValueError("threshold_sweep_hits: segment must be [Q]")
+    T, n_k = thresholds.numel(), len(k_list)
+    ks = (C.c_int32 * n_k)(*[int(k) for k in k_list])
+    dev = conf.device
+    level_hits = torch.empty((T, nseg, n_k, L), dtype=I32, device=dev)
+    err = torch.empty((1,), dtype=I32, device=dev)
+    lib = _lib.load()
+    ws = torch.empty((max(int(lib.clibd_threshold_sweep_workspace_bytes(Q, L)), 16),), dtype=torch.uint8, device=dev)
+    check(lib.clibd_threshold_sweep_hits(conf.data_ptr(), idx_a.data_ptr(), idx_b.data_ptr(), Q, m, key_labels_a.data_ptr(), Nka, key_labels_b.data_ptr(),
+                                         Nkb, query_labels.data_ptr(), L, _p(segment), nseg, thresholds.data_ptr(), T, ks, n_k, level_hits.data_ptr(),
+                                         err.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "threshold_sweep_hits")
+    e = int(err.item())
+    if e:
+        what = [msg for b, msg in ((1, "a key index outside its key table"), (2, "a negative query label"), (4, "a segment outside [0, nseg)")) if e & b]
+        raise ValueError(f"threshold_sweep_hits: {', '.join(what)}")
+    return level_hits
+
+
+def threshold_merge(conf: torch.Tensor, idx_a: torch.Tensor, idx_b: torch.Tensor, Nka: int, Nkb: int, threshold: float):
+    """clibd_threshold_merge: (merged_idx int64 [Q, m], from_a int32 [Q]) at one threshold: idx_a[q, j] where (double)conf[q, j] > threshold,
+    Nka + idx_b[q, j] otherwise (indices into the concatenated label table); bit j of from_a set when rank j came from A.  Reads one
+    error word back (a host sync): an index outside its key table raises ValueError."""
+    _chk(conf, F32, "conf")
+    _chk(idx_a, I64, "idx_a")
+    _chk(idx_b, I64, "idx_b")
+    if conf.dim() != 2 or idx_a.shape != conf.shape or idx_b.shape != conf.shape:
+        raise ValueError("threshold_merge: conf, idx_a and idx_b must be 2-D of one shape")
+    Q, m = conf.shape
+    dev = conf.device
+    merged = torch.empty((Q, m), dtype=I64, device=dev)
+    from_a = torch.empty((Q,), dtype=I32, device=dev)
+    err = torch.empty((1,), dtype=I32, device=dev)
+    check(_lib.load().clibd_threshold_merge(conf.data_ptr(), idx_a.data_ptr(), idx_b.data_ptr(), Q, m, int(Nka), int(Nkb), float(threshold),
+                                            merged.data_ptr(), from_a.data_ptr(), err.data_ptr(), _stream()), "threshold_merge")
+    if int(err.item()):
+        raise ValueError("threshold_merge: a key index outside its key table")
+    return merged, from_a
+
+
 # ------------------------------------------------------------------------------------------------ full fine-tune mode (f4)
 def layernorm_param_grads(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, dgamma: torch.Tensor, dbeta: torch.Tensor,
                           drop: Optional[Drop] = None, ordered: bool = False) -> None:

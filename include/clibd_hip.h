@@ -454,6 +454,31 @@ int clibd_topk_label_hits(const int64_t* idx, int Q, int kmax, const int32_t* ke
  * embeddings in one pass: img, dna fp32 [N, D] -> avg fp32 [N, D], cat fp32 [N, 2D].  D % 4 == 0, 16-byte aligned. */
 int clibd_eval_pair_features(const float* img, const float* dna, int N, int D, float* avg, float* cat, void* stream);
 
+/* Seen/unseen classification by a confidence threshold (additive to ABI 5; reference scripts/method_nn.py:66-91,138-164, the
+ * decide_prediction_with_threshold + top_k_micro_accuracy loops of search_threshold_with_harmonic_mean, every threshold at once).
+ * Two finished searches of the same Q queries: source A (conf fp32 [Q, m] its similarities or confidences, idx_a int64 [Q, m] into
+ * key_labels_a int32 [Nka, L]) and source B (idx_b int64 [Q, m] into key_labels_b int32 [Nkb, L]); query_labels int32 [Q, L], ids >= 0
+ * shared by both label tables; segment: optional int32 [Q] in [0, nseg) (NULL: nseg must be 1); thresholds fp64 [T] (device).  HOST:
+ * k_list int32 [n_k], strictly ascending, 1 <= k <= m <= 8, n_k <= 8, L <= 8.
+ * For threshold t the merged prediction of query q at rank j is A's key idx_a[q, j] if (double)conf[q, j] > thresholds[t], else B's key
+ * idx_b[q, j]: per position and strict, compared in fp64 (conf need not be sorted; a NaN confidence or threshold selects B, as Python's
+ * `nan > t`).  Outputs (device int32, zeroed by the call):
+ *   level_hits [T, nseg, n_k, L]  queries of the segment whose level-l label equals the merged label at some rank < k_list[i]
+ *   error [1]                     bit 0: an index of idx_a outside [0, Nka) or of idx_b outside [0, Nkb); bit 1: a negative query label;
+ *                                 bit 2: a segment outside [0, nseg).  Offending entries are never dereferenced (nor counted).
+ * workspace: clibd_threshold_sweep_workspace_bytes(Q, L) bytes (the per-(query, level) match masks), 16-byte aligned; 0 for invalid
+ * Q / L.  T * nseg * n_k * L must stay below 2^31.  Integer atomics only: the counts are exact and identical from run to run. */
+size_t clibd_threshold_sweep_workspace_bytes(int Q, int L);
+int clibd_threshold_sweep_hits(const float* conf, const int64_t* idx_a, const int64_t* idx_b, int Q, int m, const int32_t* key_labels_a, int Nka,
+                               const int32_t* key_labels_b, int Nkb, const int32_t* query_labels, int L, const int32_t* segment, int nseg,
+                               const double* thresholds, int T, const int32_t* k_list, int n_k, int32_t* level_hits, int32_t* error,
+                               void* workspace, size_t workspace_bytes, void* stream);
+/* The merged search at ONE threshold (same rule): merged_idx int64 [Q, m] = idx_a[q, j] where selected, Nka + idx_b[q, j] otherwise
+ * (indices into the concatenated label table [Nka + Nkb, L], for clibd_topk_label_hits); from_a int32 [Q]: bit j set when rank j came
+ * from A.  error [1] bit 0: an index outside its range (that entry of merged_idx is -1).  Q * m must stay below 2^31. */
+int clibd_threshold_merge(const float* conf, const int64_t* idx_a, const int64_t* idx_b, int Q, int m, int Nka, int Nkb, double threshold,
+                          int64_t* merged_idx, int32_t* from_a, int32_t* error, void* stream);
+
 /* f1 batch contract, images (additive to ABI 5): the dataset's transforms on the device, from the decoded pixels to the model's input
  * (util/dataset.py:185-195 training: ToTensor -> Resize(256, antialias) -> RandomResizedCrop(224, antialias) -> RandomHorizontalFlip ->
  * RandomVerticalFlip -> RandomRotation((-45, 45)); :216-224 eval: ToTensor -> Resize(256, antialias) -> CenterCrop(224)).
