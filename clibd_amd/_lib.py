@@ -65,26 +65,15 @@ SIGNATURES = {
     "clibd_transpose_colsum_bf16_ws": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "clibd_cast_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "clibd_cast_transpose_f32_to_bf16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "clibd_layernorm_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "clibd_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "clibd_layernorm_fwd_drop": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
-    "clibd_layernorm_bwd_drop": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
-    "clibd_layernorm_fwd_fp8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_uint32, c_int, c_float, c_void_p, c_float, c_void_p]),
-    "clibd_attention_fwd_fp8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, C.c_uint32, c_int, c_float, c_float, c_void_p]),
-    "clibd_layernorm_bwd_res16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
-    "clibd_layernorm_bwd_any": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        C.c_uint32, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-    "clibd_layernorm_bwd_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        C.c_uint32, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-    "clibd_layernorm_bwd_fp8_pg": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           C.c_uint32, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "clibd_layernorm_bwd_pg": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, C.c_uint32, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-    "clibd_attention_fwd_drop": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, C.c_uint32, c_int, c_float, c_void_p]),
-    "clibd_attention_bwd_drop": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, C.c_uint32, c_int, c_float, c_void_p]),
-    "clibd_attention_fwd_save": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, C.c_uint32, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "clibd_layernorm_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    C.c_uint32, c_int, c_float, c_void_p, c_float, c_void_p]),
+    "clibd_layernorm_bwd_pg_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    C.c_uint32, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_attention_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, C.c_uint32, c_int, c_float, c_float,
+                                    c_void_p, c_void_p, c_void_p]),
+    "clibd_attention_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, C.c_uint32, c_int, c_float, c_void_p]),
     "clibd_attention_bwd_sp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
-    "clibd_attention_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "clibd_attention_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "clibd_lora_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "clibd_lora_down_proj": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "clibd_lora_workspace_bytes": (c_size_t, [c_int, c_int]),
@@ -137,9 +126,6 @@ SIGNATURES = {
     "clibd_bert_embed_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "clibd_slice_rows_cast_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     # deterministic mode (partials workspaces + fixed-order sums)
-    "clibd_layernorm_bwd_pg_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "clibd_layernorm_bwd_pg_ordered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                               C.c_uint32, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "clibd_layernorm_param_grads_workspace_bytes": (c_size_t, [c_int, c_int]),
     "clibd_layernorm_param_grads_ordered": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, C.c_uint32, c_int, c_float,
                                                     c_void_p, c_size_t, c_void_p]),
@@ -156,7 +142,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 5   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
+ABI_VERSION = 6   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
 
 class ClibdHipError(RuntimeError):

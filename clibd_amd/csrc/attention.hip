@@ -1223,14 +1223,20 @@ using namespace clibd;
         default: MACRO(16); break;    \
     }
 
-static int attention_fwd_impl(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out,
-                              int nq, int out_seq, uint32_t drop_seed, int drop_thr16, float drop_scale, float out_fp8_scale, void* stream,
-                              float* lse = nullptr, void* o_lo = nullptr) {
+// lse / o_lo: the training forward for the single-pass backward.  The same kernels also write lse [B * nheads, S] (fp32, log2 domain)
+// and o_lo (bf16 [B * S, H]: the rounding residual of `out`); nq = S only (the backward that consumes them needs every query row).
+extern "C" int clibd_attention_fwd(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out, int nq, int out_seq,
+                                   uint32_t drop_seed, int drop_thr16, float drop_scale, float out_fp8_scale, float* lse, void* o_lo,
+                                   void* stream) {
     if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "attention_fwd: bad dropout threshold");
     if (drop_thr16 > 0 && (unsigned long long)B * nheads * S * 256ull >= (1ull << 32)) return set_error(CLIBD_EINVAL, "attention_fwd: dropout index overflow");
     if (int e = att_check(qkv, B, S, nheads, "fwd")) return e;
     if (!out) return set_error(CLIBD_EINVAL, "attention_fwd: null out");
     if (nq < 1 || nq > S || out_seq < nq) return set_error(CLIBD_EINVAL, "attention_fwd: need 1 <= nq <= S and out_seq >= nq");
+    if (!(out_fp8_scale >= 0.f)) return set_error(CLIBD_EINVAL, "attention_fwd: the fp8 scale must be 0 (bf16 out) or positive");
+    if ((lse == nullptr) != (o_lo == nullptr)) return set_error(CLIBD_EINVAL, "attention_fwd: lse / o_lo must come together");
+    if (lse && (nq != S || out_seq != S || out_fp8_scale != 0.f)) return set_error(CLIBD_EINVAL, "attention_fwd: lse / o_lo need nq = out_seq = S and a bf16 out");
+    if (lse && (!aligned16(o_lo) || ((uintptr_t)lse & 3))) return set_error(CLIBD_EINVAL, "attention_fwd: lse / o_lo alignment");
     const int nkt = 2 * ((S + 31) / 32);
     const size_t lds = (size_t)2 * nkt * 16 * 128;
     const float scale = 0.125f;  // 1/sqrt(64)
@@ -1282,15 +1288,6 @@ static int attention_fwd_impl(const void* qkv, int B, int S, int nheads, const i
     return check_launch("attention_fwd");
 }
 
-// Training forward for the single-pass backward: the same kernels, which also write lse [B * nheads, S] (fp32, log2 domain) and
-// o_lo (bf16 [B * S, H]: the rounding residual of `out`).  nq = S only (the backward that consumes them needs every query row).
-extern "C" int clibd_attention_fwd_save(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out, uint32_t drop_seed,
-                                        int drop_thr16, float drop_scale, float* lse, void* o_lo, void* stream) {
-    if (!lse || !o_lo) return set_error(CLIBD_EINVAL, "attention_fwd_save: null lse / o_lo");
-    if (!aligned16(o_lo) || ((uintptr_t)lse & 3)) return set_error(CLIBD_EINVAL, "attention_fwd_save: alignment");
-    return attention_fwd_impl(qkv, B, S, nheads, key_mask, out, S, S, drop_seed, drop_thr16, drop_scale, 0.f, stream, lse, o_lo);
-}
-
 extern "C" int clibd_attention_bwd_sp(const void* qkv, const void* dout, const void* out, const void* o_lo, const float* lse, int B, int S,
                                       int nheads, void* dqkv, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream) {
     if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "attention_bwd_sp: bad dropout threshold");
@@ -1324,26 +1321,9 @@ extern "C" int clibd_attention_bwd_sp(const void* qkv, const void* dout, const v
     return check_launch("attention_bwd_sp");
 }
 
-extern "C" int clibd_attention_fwd_drop(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out,
-                                        int nq, int out_seq, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream) {
-    return attention_fwd_impl(qkv, B, S, nheads, key_mask, out, nq, out_seq, drop_seed, drop_thr16, drop_scale, 0.f, stream);
-}
-
-extern "C" int clibd_attention_fwd_fp8(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out_fp8,
-                                       int nq, int out_seq, uint32_t drop_seed, int drop_thr16, float drop_scale, float out_fp8_scale,
-                                       void* stream) {
-    if (!(out_fp8_scale > 0.f)) return set_error(CLIBD_EINVAL, "attention_fwd_fp8: scale must be positive");
-    return attention_fwd_impl(qkv, B, S, nheads, key_mask, out_fp8, nq, out_seq, drop_seed, drop_thr16, drop_scale, out_fp8_scale, stream);
-}
-
-extern "C" int clibd_attention_fwd(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out,
-                                   int nq, int out_seq, void* stream) {
-    return clibd_attention_fwd_drop(qkv, B, S, nheads, key_mask, out, nq, out_seq, 0u, 0, 1.0f, stream);
-}
-
-extern "C" int clibd_attention_bwd_drop(const void* qkv, const void* dout, int B, int S, int nheads, const int32_t* key_mask,
-                                        void* dqkv, int nq, int dout_seq, uint32_t drop_seed, int drop_thr16, float drop_scale,
-                                        void* stream) {
+extern "C" int clibd_attention_bwd(const void* qkv, const void* dout, int B, int S, int nheads, const int32_t* key_mask,
+                                   void* dqkv, int nq, int dout_seq, uint32_t drop_seed, int drop_thr16, float drop_scale,
+                                   void* stream) {
     if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "attention_bwd: bad dropout threshold");
     if (drop_thr16 > 0 && (unsigned long long)B * nheads * S * 256ull >= (1ull << 32)) return set_error(CLIBD_EINVAL, "attention_bwd: dropout index overflow");
     if (int e = att_check(qkv, B, S, nheads, "bwd")) return e;
@@ -1391,11 +1371,6 @@ extern "C" int clibd_attention_bwd_drop(const void* qkv, const void* dout, int B
 #undef LAUNCH
 #undef LAUNCH_M
     return check_launch("attention_bwd");
-}
-
-extern "C" int clibd_attention_bwd(const void* qkv, const void* dout, int B, int S, int nheads, const int32_t* key_mask,
-                                   void* dqkv, int nq, int dout_seq, void* stream) {
-    return clibd_attention_bwd_drop(qkv, dout, B, S, nheads, key_mask, dqkv, nq, dout_seq, 0u, 0, 1.0f, stream);
 }
 
 #ifdef CLIBD_GEMM_DIAG

@@ -453,7 +453,7 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_bf16_kernel(const unsig
                      fmaxf(fabsf(bf2f((unsigned short)(pk.y & 0xffff))), fabsf(bf2f((unsigned short)(pk.y >> 16)))));
     }
     amax = wave_max(amax);
-    // a power-of-two scale, s = 2^(7 - floor(log2 amax)) (the row-scale rule of clibd_layernorm_bwd_fp8: scaled maximum in [128, 256)):
+    // a power-of-two scale, s = 2^(7 - floor(log2 amax)) (the row-scale rule of clibd_layernorm_bwd's dx_fp8: scaled maximum in [128, 256)):
     // exact in every arithmetic, so the image does not depend on how a division rounds — bf16 inputs sit ON e4m3 rounding ties
     // under the 448 / amax scale of the fp32 quantiser (w / amax is a ratio of 8-bit integers)
     float s = 1.f;

@@ -69,13 +69,13 @@ __device__ __forceinline__ i32x8 cat_frag(bf16x8 lo, bf16x8 hi) {
 }
 
 // DG (8-bit dgrad, round 5; FP8 only): the A operand is a GRADIENT as e4m3 bytes with one power-of-two scale per ROW (written by
-// clibd_layernorm_bwd_fp8), W the transposed frozen weight as e4m3 with one scale per row (= per input channel of the layer).
+// clibd_layernorm_bwd with dx_fp8), W the transposed frozen weight as e4m3 with one scale per row (= per input channel of the layer).
 //   EPI_BF16 / EPI_ADD_AUX: v = acc * col_scale[n] * a_row_dequant[m]  [+ aux]  -> out_bf16
 //   EPI_MUL_AUX[_U8]      : out := e4m3(acc * col_scale[n] * aux[m,n] * out_fp8_scale) bytes (aux = gelu' as bf16, or as the one-byte code of §4) — the row scale of A passes THROUGH to the
 //                           output (the next dgrad's A operand, dequantised by the same a_row_dequant; 1 / out_fp8_scale rides in its col_scale).
 //   DG == 2 (round 6, full fine-tune; MUL_AUX kinds): additionally p.dual_bf16[m,n] = bf16(acc * col_scale[n] * aux[m,n] * a_row_dequant[m]) — the
 //                           true d(fc1 out), which the bf16 weight gradient of fc1 contracts with its input.  The row factors are powers of two
-//                           (clibd_layernorm_bwd_fp8 writes 2^(e - 134)): a lane keeps the four exponents of a row group in ONE register.
+//                           (clibd_layernorm_bwd writes 2^(e - 134)): a lane keeps the four exponents of a row group in ONE register.
 // SK (round 6): the stream-K tail — the last, partial round's tiles cut into K-slices over the idle CUs (GemmParams.sk_*); bf16 kinds only.
 template <int KIND, bool LORA, bool BIAS, bool DIAG, bool FP8, int DG, bool SK = false>
 __device__ __forceinline__ void gemm256_body(const GemmParams& p, int ntiles, int skew_ticks, long long* stamps) {

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 }
 
 // dx = rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy * gamma ;  optional + dres
-// The residual gradient may travel as bf16 instead of fp32 (clibd_layernorm_bwd_res16): dres_b16 is then the incoming stream
+// The residual gradient may travel as bf16 instead of fp32 (dres_bf16 / dx_res_bf16 of the C ABI): dres_b16 is then the incoming stream
 // and dx_res_b16 an un-dropped bf16 copy of the result (the gradient of the residual sum; dx_bf16 carries the dropout mask of
 // the dense branch when one is active) — 10 instead of 16 bytes per element for a pre-LN block.
 // PG (full fine-tune mode): also dgamma[c] += sum_rows dy * xhat, dbeta[c] += sum_rows dy — the kernel has dy and xhat in
@@ -409,9 +409,9 @@ using namespace clibd;
 // rows per wave and iteration (A/B at M = 403 456, H = 768: with the down-projection 479 -> 392 us at 2 rows, 391 at 4; without it
 // 352-363 -> 335-347 us at 2, 330 at 4; profiles/r03_exp_layernorm_rows.log)
 constexpr int LN_FWD_ROWS_LORA = 2, LN_FWD_ROWS_PLAIN = 4;
-static int layernorm_fwd_impl(const float* x, int M, int H, const float* gamma, const float* beta, float eps,
-                              void* y_bf16, float* y_f32, float* stats, const void* lora_a_bf16, void* t_bf16,
-                              uint32_t drop_seed, int drop_thr16, float drop_scale, void* y_fp8, float fp8_scale, void* stream) {
+extern "C" int clibd_layernorm_fwd(const float* x, int M, int H, const float* gamma, const float* beta, float eps,
+                                   void* y_bf16, float* y_f32, float* stats, const void* lora_a_bf16, void* t_bf16,
+                                   uint32_t drop_seed, int drop_thr16, float drop_scale, void* y_fp8, float fp8_scale, void* stream) {
     if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "layernorm_fwd: bad dropout threshold");
     if (!x || !gamma || !beta) return set_error(CLIBD_EINVAL, "layernorm_fwd: null pointer");
     if (M <= 0 || H <= 0 || H % 64 != 0 || H > 1024) return set_error(CLIBD_EINVAL, "layernorm_fwd: H must be a multiple of 64, <= 1024");
@@ -447,30 +447,18 @@ static int layernorm_fwd_impl(const float* x, int M, int H, const float* gamma, 
     return check_launch("layernorm_fwd");
 }
 
-extern "C" int clibd_layernorm_fwd_drop(const float* x, int M, int H, const float* gamma, const float* beta, float eps,
-                                        void* y_bf16, float* y_f32, float* stats, const void* lora_a_bf16, void* t_bf16,
-                                        uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream) {
-    return layernorm_fwd_impl(x, M, H, gamma, beta, eps, y_bf16, y_f32, stats, lora_a_bf16, t_bf16, drop_seed, drop_thr16, drop_scale, nullptr, 0.f, stream);
+// ---- backward. Deterministic mode: with a workspace the parameter-gradient forms write one [2, H] partial per block of the PG grid
+// (min(ceil(M / 4), 1024) blocks: a function of the shape only) instead of float atomics, then ordered_colsum_kernel adds the rows in
+// block order into dgamma / dbeta.
+extern "C" size_t clibd_layernorm_bwd_pg_workspace_bytes(int M, int H) {
+    if (M <= 0 || H <= 0) return 0;
+    return (size_t)min((M + 3) / 4, 1024) * 2 * (size_t)H * sizeof(float);
 }
 
-extern "C" int clibd_layernorm_fwd(const float* x, int M, int H, const float* gamma, const float* beta, float eps,
-                                   void* y_bf16, float* y_f32, float* stats, const void* lora_a_bf16,
-                                   void* t_bf16, void* stream) {
-    return layernorm_fwd_impl(x, M, H, gamma, beta, eps, y_bf16, y_f32, stats, lora_a_bf16, t_bf16, 0u, 0, 1.0f, nullptr, 0.f, stream);
-}
-
-extern "C" int clibd_layernorm_fwd_fp8(const float* x, int M, int H, const float* gamma, const float* beta, float eps,
-                                       void* y_bf16, float* y_f32, float* stats, const void* lora_a_bf16, void* t_bf16,
-                                       uint32_t drop_seed, int drop_thr16, float drop_scale, void* y_fp8, float fp8_scale, void* stream) {
-    if (!y_fp8) return set_error(CLIBD_EINVAL, "layernorm_fwd_fp8: null y_fp8");
-    return layernorm_fwd_impl(x, M, H, gamma, beta, eps, y_bf16, y_f32, stats, lora_a_bf16, t_bf16, drop_seed, drop_thr16, drop_scale, y_fp8, fp8_scale, stream);
-}
-
-static int layernorm_bwd_impl(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats,
-                              const float* gamma, int M, int H, const float* dres_f32, float* dx_f32,
-                              void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, float* dgamma, float* dbeta, void* stream,
-                              const void* dres_b16 = nullptr, void* dx_res_b16 = nullptr, void* dx_fp8 = nullptr, float* row_dequant = nullptr,
-                              float* pg_ws = nullptr) {
+extern "C" int clibd_layernorm_bwd(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
+                                   int M, int H, const float* dres_f32, const void* dres_b16, float* dx_f32, void* dx_res_b16,
+                                   void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* dx_fp8, float* row_dequant,
+                                   float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
     if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "layernorm_bwd: bad dropout threshold");
     if (!x || !stats || !gamma) return set_error(CLIBD_EINVAL, "layernorm_bwd: null pointer");
     if ((dy_bf16 == nullptr) == (dy_f32 == nullptr)) return set_error(CLIBD_EINVAL, "layernorm_bwd: exactly one of dy_bf16/dy_f32");
@@ -481,6 +469,12 @@ static int layernorm_bwd_impl(const void* dy_bf16, const float* dy_f32, const fl
     if (dres_f32 && dres_b16) return set_error(CLIBD_EINVAL, "layernorm_bwd: the residual gradient is either fp32 or bf16");
     if (((uintptr_t)dres_b16 & 7) || ((uintptr_t)dx_res_b16 & 7)) return set_error(CLIBD_EINVAL, "layernorm_bwd: alignment");
     if ((dgamma == nullptr) != (dbeta == nullptr)) return set_error(CLIBD_EINVAL, "layernorm_bwd: dgamma/dbeta must come together");
+    if (workspace && !dgamma) return set_error(CLIBD_EINVAL, "layernorm_bwd: a workspace needs dgamma / dbeta");
+    if (!workspace && workspace_bytes > 0) return set_error(CLIBD_EINVAL, "layernorm_bwd: null workspace with workspace_bytes > 0");
+    if (workspace && ((uintptr_t)workspace & 15)) return set_error(CLIBD_EINVAL, "layernorm_bwd: misaligned workspace");
+    if (workspace && workspace_bytes < clibd_layernorm_bwd_pg_workspace_bytes(M, H))
+        return set_error(CLIBD_EINVAL, "layernorm_bwd: workspace too small (clibd_layernorm_bwd_pg_workspace_bytes)");
+    float* pg_ws = (float*)workspace;
     const int nch = (H + 255) / 256;
     const bool pg = dgamma != nullptr;
     // parameter-gradient mode: at most 4 blocks per CU-slot (1024 blocks): 2 x H float atomics per block stay ~1.5 M per launch
@@ -527,79 +521,4 @@ static int layernorm_bwd_impl(const void* dy_bf16, const float* dy_f32, const fl
 #undef LAUNCH_R
     if (int e = check_launch("layernorm_bwd")) return e;
     return pg_ws != nullptr ? ordered_colsum_launch(pg_ws, (int)grid.x, 2 * H, dgamma, H, dbeta, st) : CLIBD_OK;
-}
-
-extern "C" int clibd_layernorm_bwd_drop(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats,
-                                        const float* gamma, int M, int H, const float* dres_f32, float* dx_f32,
-                                        void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream) {
-    return layernorm_bwd_impl(dy_bf16, dy_f32, x, stats, gamma, M, H, dres_f32, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, nullptr,
-                              nullptr, stream);
-}
-
-extern "C" int clibd_layernorm_bwd(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats,
-                                   const float* gamma, int M, int H, const float* dres_f32, float* dx_f32,
-                                   void* dx_bf16, void* stream) {
-    return layernorm_bwd_impl(dy_bf16, dy_f32, x, stats, gamma, M, H, dres_f32, dx_f32, dx_bf16, 0u, 0, 1.0f, nullptr, nullptr, stream);
-}
-
-extern "C" int clibd_layernorm_bwd_pg(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats,
-                                      const float* gamma, int M, int H, const float* dres_f32, float* dx_f32,
-                                      void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, float* dgamma, float* dbeta,
-                                      void* stream) {
-    if (!dgamma || !dbeta) return set_error(CLIBD_EINVAL, "layernorm_bwd_pg: null dgamma/dbeta");
-    return layernorm_bwd_impl(dy_bf16, dy_f32, x, stats, gamma, M, H, dres_f32, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, dgamma, dbeta,
-                              stream);
-}
-
-extern "C" int clibd_layernorm_bwd_res16(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats,
-                                         const float* gamma, int M, int H, const void* dres_bf16, void* dx_res_bf16,
-                                         void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream) {
-    return layernorm_bwd_impl(dy_bf16, dy_f32, x, stats, gamma, M, H, nullptr, nullptr, dx_bf16, drop_seed, drop_thr16, drop_scale, nullptr,
-                              nullptr, stream, dres_bf16, dx_res_bf16);
-}
-
-extern "C" int clibd_layernorm_bwd_fp8(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
-                                       int M, int H, const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16,
-                                       void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* dx_fp8, float* row_dequant,
-                                       void* stream) {
-    if (!dx_fp8 || !row_dequant) return set_error(CLIBD_EINVAL, "layernorm_bwd_fp8: null dx_fp8 / row_dequant");
-    return layernorm_bwd_impl(dy_bf16, dy_f32, x, stats, gamma, M, H, dres_f32, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, nullptr,
-                              nullptr, stream, dres_bf16, dx_res_bf16, dx_fp8, row_dequant);
-}
-
-extern "C" int clibd_layernorm_bwd_fp8_pg(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
-                                          int M, int H, const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16,
-                                          void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* dx_fp8, float* row_dequant,
-                                          float* dgamma, float* dbeta, void* stream) {
-    if (!dx_fp8 || !row_dequant || !dgamma || !dbeta) return set_error(CLIBD_EINVAL, "layernorm_bwd_fp8_pg: null dx_fp8 / row_dequant / dgamma / dbeta");
-    return layernorm_bwd_impl(dy_bf16, dy_f32, x, stats, gamma, M, H, dres_f32, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, dgamma,
-                              dbeta, stream, dres_bf16, dx_res_bf16, dx_fp8, row_dequant);
-}
-
-extern "C" int clibd_layernorm_bwd_any(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
-                                       int M, int H, const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16,
-                                       void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, float* dgamma, float* dbeta,
-                                       void* stream) {
-    return layernorm_bwd_impl(dy_bf16, dy_f32, x, stats, gamma, M, H, dres_f32, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, dgamma,
-                              dbeta, stream, dres_bf16, dx_res_bf16);
-}
-
-// ---- deterministic mode: the parameter-gradient forms with a partials workspace instead of float atomics ---------------------------------
-// One [2, H] partial per block of the PG grid (min(ceil(M / 4), 1024) blocks: a function of the shape only), then ordered_colsum_kernel
-// adds the rows in block order into dgamma / dbeta.
-extern "C" size_t clibd_layernorm_bwd_pg_workspace_bytes(int M, int H) {
-    if (M <= 0 || H <= 0) return 0;
-    return (size_t)min((M + 3) / 4, 1024) * 2 * (size_t)H * sizeof(float);
-}
-
-extern "C" int clibd_layernorm_bwd_pg_ordered(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
-                                              int M, int H, const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16,
-                                              void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* dx_fp8, float* row_dequant,
-                                              float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!dgamma || !dbeta) return set_error(CLIBD_EINVAL, "layernorm_bwd_pg_ordered: null dgamma / dbeta");
-    if (!workspace || ((uintptr_t)workspace & 15)) return set_error(CLIBD_EINVAL, "layernorm_bwd_pg_ordered: null or misaligned workspace");
-    if (M <= 0 || H <= 0 || workspace_bytes < clibd_layernorm_bwd_pg_workspace_bytes(M, H))
-        return set_error(CLIBD_EINVAL, "layernorm_bwd_pg_ordered: bad shape or workspace too small (clibd_layernorm_bwd_pg_workspace_bytes)");
-    return layernorm_bwd_impl(dy_bf16, dy_f32, x, stats, gamma, M, H, dres_f32, dx_f32, dx_bf16, drop_seed, drop_thr16, drop_scale, dgamma,
-                              dbeta, stream, dres_bf16, dx_res_bf16, dx_fp8, row_dequant, (float*)workspace);
 }

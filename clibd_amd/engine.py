@@ -81,7 +81,7 @@ class NotSupportedYet(NotImplementedError):
 #   the mean-pooled towers, 0.987-0.9998 with the ViT's too; SimpleCLIP.enable_fp8_dgrad selects towers).  The bf16 residual-gradient stream only
 #   (gelu' as bf16 or as its one-byte code); a call whose token count is not a multiple of 4 takes the bf16 GEMMs.  Round 6: also with TRAINABLE base
 #   weights (disable_lora, the reference's final recipe) — the e4m3 weight images are re-made every step, the LayerNorm backward writes the e4m3 rows
-#   AND the bf16 copy the weight gradient contracts (clibd_layernorm_bwd_fp8_pg), the fc2 dgrad writes d(fc1 out) as e4m3 AND as bf16; every weight /
+#   AND the bf16 copy the weight gradient contracts (clibd_layernorm_bwd with dx_fp8 and dgamma / dbeta), the fc2 dgrad writes d(fc1 out) as e4m3 AND as bf16; every weight /
 #   bias / LayerNorm gradient is the bf16 path's arithmetic on those copies.  DESIGN.md §3.1d.
 NUMERICS_CHOICES = dict(residual_grad=("bf16", "fp32"), gelu_grad=("bf16", "u8", "e4m7"), attn_bwd=("2phase", "sp"), ln_fold=("off", "on"),
                         dgrad=("bf16", "fp8"))
@@ -672,7 +672,7 @@ class TransformerStack:
         if full:
             first_lora = -1  # every layer has trainable parameters and the input gradient is needed
         # bf16 residual-gradient stream (see NUMERICS_CHOICES).  Round 4: full fine-tune mode takes it too — the LayerNorm parameter
-        # gradients ride along in the same kernel (clibd_layernorm_bwd_any), and the BOTTOM layer hands an fp32 gradient to the
+        # gradients ride along in the same kernel (clibd_layernorm_bwd with dgamma / dbeta), and the BOTTOM layer hands an fp32 gradient to the
         # embedding backward as before (`need32`).  409.6 ms per step at b = 2048 with the fp32 stream (profiles/r04_fullft_*_v1*).
         r16 = self.numerics["residual_grad"] == "bf16"
         # 8-bit dgrad (numerics dgrad = "fp8"): every LayerNorm backward below also writes its output as e4m3 rows + one dequantisation

@@ -59,6 +59,11 @@ class Drop:
         self.scale = 1.0 / (1.0 - self.thr16 / 65536.0)
 
 
+def _drop_args(drop: Optional[Drop]) -> tuple:
+    """(seed, thr16, scale) of a dropout site for the C ABI; no site or p = 0: dropout off"""
+    return (drop.seed, drop.thr16, drop.scale) if (drop is not None and drop.thr16 > 0) else (0, 0, 1.0)
+
+
 def derive_seed(base: int, layer: int, site: int) -> int:
     """site seeds of one tower call (site: 0 attention probs, 1 attention-output dropout, 2 output dropout, 3 embeddings)"""
     x = (base ^ ((layer * 8 + site + 1) * 0x9E3779B1)) & 0xFFFFFFFF
@@ -429,159 +434,46 @@ def layernorm_fwd(x, gamma, beta, eps, *, y_bf16=None, y_f32=None, stats=None, l
             _chk(t, dt, nm)
             if tuple(t.shape) != shape:
                 raise ValueError(f"layernorm_fwd: {nm} must be {shape}, got {tuple(t.shape)}")
-    if y_fp8 is not None:
-        d = drop if (drop is not None and drop.thr16 > 0) else Drop(0.0, 0)
-        check(_lib.load().clibd_layernorm_fwd_fp8(x.data_ptr(), M, H, gamma.data_ptr(), beta.data_ptr(), float(eps), _p(y_bf16), _p(y_f32),
-                                                  _p(stats), _p(lora_a), _p(t_out), d.seed, d.thr16, d.scale, y_fp8.data_ptr(), float(fp8_scale),
-                                                  _stream()), "layernorm_fwd_fp8")
-        return
-    if drop is not None and drop.thr16 > 0:
-        check(_lib.load().clibd_layernorm_fwd_drop(x.data_ptr(), M, H, gamma.data_ptr(), beta.data_ptr(), float(eps), _p(y_bf16), _p(y_f32),
-                                                   _p(stats), _p(lora_a), _p(t_out), drop.seed, drop.thr16, drop.scale, _stream()),
-              "layernorm_fwd_drop")
-        return
     check(_lib.load().clibd_layernorm_fwd(x.data_ptr(), M, H, gamma.data_ptr(), beta.data_ptr(), float(eps), _p(y_bf16), _p(y_f32),
-                                          _p(stats), _p(lora_a), _p(t_out), _stream()), "layernorm_fwd")
+                                          _p(stats), _p(lora_a), _p(t_out), *_drop_args(drop), _p(y_fp8), float(fp8_scale), _stream()),
+          "layernorm_fwd")
 
 
 def layernorm_bwd(dy, x, stats, gamma, *, dres=None, dx_f32=None, dx_bf16=None, drop=None, dgamma=None, dbeta=None,
                   dres_bf16=None, dx_res_bf16=None, dx_fp8=None, row_dequant=None, ordered: bool = False) -> None:
-    """dgamma / dbeta (fp32 [H], accumulate): the LayerNorm parameter gradients in the same pass (full fine-tune mode).
-    dres_bf16 / dx_res_bf16: the residual gradient travels as bf16 (clibd_layernorm_bwd_res16): dx = LN'(dy) + dres_bf16,
-    dx_res_bf16 = bf16(dx) without the dropout mask that dx_bf16 carries; no fp32 input / output stream then.
-    dx_fp8 [M,H] e4m3 + row_dequant [M] fp32 (8-bit dgrad, clibd_layernorm_bwd_fp8): the dx_bf16 values once more as the A operand of
-    gemm_fp8_dgrad_nt, one power-of-two scale per row; dx_bf16 itself becomes optional.
-    ordered (with dgamma / dbeta): the parameter gradients as per-block partials summed in block order (clibd_layernorm_bwd_pg_ordered)."""
+    """dx = LN'(dy) [+ dres | dres_bf16] into dx_f32 / dx_bf16 / dx_res_bf16 (at least one); see clibd_layernorm_bwd in include/clibd_hip.h.
+    dgamma / dbeta (fp32 [H], accumulate): the LayerNorm parameter gradients in the same pass (full fine-tune mode).
+    dres_bf16 / dx_res_bf16: the residual gradient travels as bf16: dx = LN'(dy) + dres_bf16, dx_res_bf16 = bf16(dx) without the
+    dropout mask that dx_bf16 carries.
+    dx_fp8 [M,H] e4m3 + row_dequant [M] fp32 (8-bit dgrad): the dx_bf16 values once more as the A operand of gemm_fp8_dgrad_nt, one
+    power-of-two scale per row; dx_bf16 itself becomes optional.
+    ordered (with dgamma / dbeta): the parameter gradients as per-block partials summed in block order."""
     _chk(x, F32, "x")
     M, H = x.shape
-    if ordered and dgamma is not None:
-        _layernorm_bwd_pg_ordered(dy, x, stats, gamma, M, H, dres, dx_f32, dx_bf16, drop, dgamma, dbeta, dres_bf16, dx_res_bf16, dx_fp8, row_dequant)
-        return
-    if dx_fp8 is not None or row_dequant is not None:
-        if dx_fp8 is None or row_dequant is None or (dgamma is None) != (dbeta is None):
-            raise ValueError("layernorm_bwd: dx_fp8 and row_dequant come together (and dgamma with dbeta)")
-        _chk(dx_fp8, FP8, "dx_fp8")
-        _chk(row_dequant, F32, "row_dequant")
-        if tuple(dx_fp8.shape) != (M, H) or row_dequant.numel() != M:
-            raise ValueError("layernorm_bwd: dx_fp8 must be [M,H], row_dequant [M]")
-        for nm, t, dt in (("dres", dres, F32), ("dres_bf16", dres_bf16, BF16), ("dx_f32", dx_f32, F32), ("dx_res_bf16", dx_res_bf16, BF16), ("dx_bf16", dx_bf16, BF16)):
-            if t is not None:
-                _chk(t, dt, nm)
-                if tuple(t.shape) != (M, H):
-                    raise ValueError(f"layernorm_bwd: {nm} shape")
-        if dy.dtype not in (BF16, F32) or tuple(dy.shape) != (M, H):
-            raise ValueError("layernorm_bwd: dy must be bf16 or fp32 [M,H]")
-        _chk(dy, dy.dtype, "dy")
-        _chk(stats, F32, "stats")
-        _chk(gamma, F32, "gamma")
-        d = drop if (drop is not None and drop.thr16 > 0) else Drop(0.0, 0)
-        dyb, dyf = (dy.data_ptr(), None) if dy.dtype == BF16 else (None, dy.data_ptr())
-        if dgamma is not None:   # full fine-tune under the 8-bit dgrad: the parameter gradients ride along (clibd_layernorm_bwd_fp8_pg)
-            _chk(dgamma, F32, "dgamma"); _chk(dbeta, F32, "dbeta")
-            if dgamma.numel() != H or dbeta.numel() != H:
-                raise ValueError("layernorm_bwd: dgamma / dbeta must have H elements")
-            check(_lib.load().clibd_layernorm_bwd_fp8_pg(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres), _p(dres_bf16), _p(dx_f32),
-                                                         _p(dx_res_bf16), _p(dx_bf16), d.seed, d.thr16, d.scale, dx_fp8.data_ptr(), row_dequant.data_ptr(),
-                                                         dgamma.data_ptr(), dbeta.data_ptr(), _stream()), "layernorm_bwd_fp8_pg")
-            return
-        check(_lib.load().clibd_layernorm_bwd_fp8(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres), _p(dres_bf16), _p(dx_f32),
-                                                  _p(dx_res_bf16), _p(dx_bf16), d.seed, d.thr16, d.scale, dx_fp8.data_ptr(), row_dequant.data_ptr(),
-                                                  _stream()), "layernorm_bwd_fp8")
-        return
-    if dres_bf16 is not None or dx_res_bf16 is not None:
-        if dres is not None:
-            raise ValueError("layernorm_bwd: the residual gradient is either fp32 (dres) or bf16 (dres_bf16)")
-        for nm, t in (("dres_bf16", dres_bf16), ("dx_res_bf16", dx_res_bf16), ("dx_bf16", dx_bf16)):
-            if t is not None:
-                _chk(t, BF16, nm)
-                if tuple(t.shape) != (M, H):
-                    raise ValueError(f"layernorm_bwd: {nm} shape")
-        _chk(dy, dy.dtype if dy.dtype in (BF16, F32) else BF16, "dy")
-        if tuple(dy.shape) != (M, H):
-            raise ValueError("layernorm_bwd: dy shape")
-        _chk(stats, F32, "stats")
-        _chk(gamma, F32, "gamma")
-        d = drop if (drop is not None and drop.thr16 > 0) else Drop(0.0, 0)
-        dyb, dyf = (dy.data_ptr(), None) if dy.dtype == BF16 else (None, dy.data_ptr())
-        if dx_f32 is not None or dgamma is not None or dbeta is not None:
-            # full fine-tune on the bf16 stream: parameter gradients ride along, the bottom layer hands an fp32 gradient to the embeddings
-            if dx_f32 is not None:
-                _chk(dx_f32, F32, "dx_f32")
-                if tuple(dx_f32.shape) != (M, H):
-                    raise ValueError("layernorm_bwd: dx_f32 shape")
-            if (dgamma is None) != (dbeta is None):
-                raise ValueError("layernorm_bwd: dgamma / dbeta come together")
-            if dgamma is not None:
-                _chk(dgamma, F32, "dgamma"); _chk(dbeta, F32, "dbeta")
-                if dgamma.numel() != H or dbeta.numel() != H:
-                    raise ValueError("layernorm_bwd: dgamma / dbeta must have H elements")
-            check(_lib.load().clibd_layernorm_bwd_any(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, None, _p(dres_bf16), _p(dx_f32),
-                                                      _p(dx_res_bf16), _p(dx_bf16), d.seed, d.thr16, d.scale, _p(dgamma), _p(dbeta), _stream()),
-                  "layernorm_bwd_any")
-            return
-        check(_lib.load().clibd_layernorm_bwd_res16(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres_bf16), _p(dx_res_bf16),
-                                                    _p(dx_bf16), d.seed, d.thr16, d.scale, _stream()), "layernorm_bwd_res16")
-        return
-    if dy.dtype == BF16:
-        _chk(dy, BF16, "dy")
-        dyb, dyf = dy.data_ptr(), None
-    else:
-        _chk(dy, F32, "dy")
-        dyb, dyf = None, dy.data_ptr()
-    if tuple(dy.shape) != (M, H):
-        raise ValueError("layernorm_bwd: dy shape")
+    if dy.dtype not in (BF16, F32):
+        raise ValueError("layernorm_bwd: dy must be bf16 or fp32")
     _chk(stats, F32, "stats")
     _chk(gamma, F32, "gamma")
-    for nm, t, dt in (("dres", dres, F32), ("dx_f32", dx_f32, F32), ("dx_bf16", dx_bf16, BF16)):
+    for nm, t, dt, shape in (("dy", dy, dy.dtype, (M, H)), ("dres", dres, F32, (M, H)), ("dres_bf16", dres_bf16, BF16, (M, H)),
+                             ("dx_f32", dx_f32, F32, (M, H)), ("dx_res_bf16", dx_res_bf16, BF16, (M, H)), ("dx_bf16", dx_bf16, BF16, (M, H)),
+                             ("dx_fp8", dx_fp8, FP8, (M, H)), ("row_dequant", row_dequant, F32, (M,)), ("dgamma", dgamma, F32, (H,)),
+                             ("dbeta", dbeta, F32, (H,))):
         if t is not None:
             _chk(t, dt, nm)
-            if tuple(t.shape) != (M, H):
-                raise ValueError(f"layernorm_bwd: {nm} shape")
-    if dgamma is not None or dbeta is not None:
-        _chk(dgamma, F32, "dgamma"); _chk(dbeta, F32, "dbeta")
-        if dgamma.numel() != H or dbeta.numel() != H:
-            raise ValueError("layernorm_bwd: dgamma / dbeta must have H elements")
-        d = drop if (drop is not None and drop.thr16 > 0) else Drop(0.0, 0)
-        check(_lib.load().clibd_layernorm_bwd_pg(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres), _p(dx_f32),
-                                                 _p(dx_bf16), d.seed, d.thr16, d.scale, dgamma.data_ptr(), dbeta.data_ptr(), _stream()),
-              "layernorm_bwd_pg")
-        return
-    if drop is not None and drop.thr16 > 0:
-        check(_lib.load().clibd_layernorm_bwd_drop(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres), _p(dx_f32),
-                                                   _p(dx_bf16), drop.seed, drop.thr16, drop.scale, _stream()), "layernorm_bwd_drop")
-        return
-    check(_lib.load().clibd_layernorm_bwd(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres), _p(dx_f32),
-                                          _p(dx_bf16), _stream()), "layernorm_bwd")
-
-
-def _layernorm_bwd_pg_ordered(dy, x, stats, gamma, M, H, dres, dx_f32, dx_bf16, drop, dgamma, dbeta, dres_bf16, dx_res_bf16, dx_fp8, row_dequant):
-    if dbeta is None or (dx_fp8 is None) != (row_dequant is None):
-        raise ValueError("layernorm_bwd: dgamma with dbeta, dx_fp8 with row_dequant")
+            if tuple(t.shape) != shape and (len(shape) == 2 or t.numel() != shape[0]):   # the vectors: any shape of that many elements
+                raise ValueError(f"layernorm_bwd: {nm} must be {shape}, got {tuple(t.shape)}")
+    if (dx_fp8 is None) != (row_dequant is None) or (dgamma is None) != (dbeta is None):
+        raise ValueError("layernorm_bwd: dx_fp8 comes with row_dequant, dgamma with dbeta")
     if dres is not None and dres_bf16 is not None:
         raise ValueError("layernorm_bwd: the residual gradient is either fp32 (dres) or bf16 (dres_bf16)")
-    if dy.dtype not in (BF16, F32) or tuple(dy.shape) != (M, H):
-        raise ValueError("layernorm_bwd: dy must be bf16 or fp32 [M,H]")
-    _chk(dy, dy.dtype, "dy"); _chk(stats, F32, "stats"); _chk(gamma, F32, "gamma"); _chk(dgamma, F32, "dgamma"); _chk(dbeta, F32, "dbeta")
-    if dgamma.numel() != H or dbeta.numel() != H:
-        raise ValueError("layernorm_bwd: dgamma / dbeta must have H elements")
-    for nm, t, dt in (("dres", dres, F32), ("dres_bf16", dres_bf16, BF16), ("dx_f32", dx_f32, F32), ("dx_res_bf16", dx_res_bf16, BF16),
-                      ("dx_bf16", dx_bf16, BF16), ("dx_fp8", dx_fp8, FP8)):
-        if t is not None:
-            _chk(t, dt, nm)
-            if tuple(t.shape) != (M, H):
-                raise ValueError(f"layernorm_bwd: {nm} shape")
-    if row_dequant is not None:
-        _chk(row_dequant, F32, "row_dequant")
-        if row_dequant.numel() != M:
-            raise ValueError("layernorm_bwd: row_dequant must have M elements")
-    d = drop if (drop is not None and drop.thr16 > 0) else Drop(0.0, 0)
-    dyb, dyf = (dy.data_ptr(), None) if dy.dtype == BF16 else (None, dy.data_ptr())
+    if dx_f32 is None and dx_bf16 is None and dx_res_bf16 is None and dx_fp8 is None:
+        raise ValueError("layernorm_bwd: no output")
     lib = _lib.load()
-    need = int(lib.clibd_layernorm_bwd_pg_workspace_bytes(M, H))
-    ws = _ordered_workspace("ln_pg", need, x.device)
-    check(lib.clibd_layernorm_bwd_pg_ordered(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres), _p(dres_bf16), _p(dx_f32),
-                                             _p(dx_res_bf16), _p(dx_bf16), d.seed, d.thr16, d.scale, _p(dx_fp8), _p(row_dequant),
-                                             dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "layernorm_bwd_pg_ordered")
+    ws = _ordered_workspace("ln_pg", int(lib.clibd_layernorm_bwd_pg_workspace_bytes(M, H)), x.device) if ordered and dgamma is not None else None
+    dyb, dyf = (dy.data_ptr(), None) if dy.dtype == BF16 else (None, dy.data_ptr())
+    check(lib.clibd_layernorm_bwd(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres), _p(dres_bf16), _p(dx_f32),
+                                  _p(dx_res_bf16), _p(dx_bf16), *_drop_args(drop), _p(dx_fp8), _p(row_dequant), _p(dgamma), _p(dbeta),
+                                  _p(ws), 0 if ws is None else ws.numel(), _stream()), "layernorm_bwd")
 
 
 def attention_fwd(qkv: torch.Tensor, B: int, S: int, nheads: int, key_mask: Optional[torch.Tensor], out: torch.Tensor,
@@ -589,39 +481,23 @@ def attention_fwd(qkv: torch.Tensor, B: int, S: int, nheads: int, key_mask: Opti
                   o_lo: Optional[torch.Tensor] = None) -> None:
     """nq: evaluate only the first nq query rows of every sequence; `out` is then [B*nq, H].
     out_fp8_scale > 0 (fp8-forward mode): `out` is float8_e4m3fn and receives e4m3(o * out_fp8_scale).
-    lse (fp32 [B*nheads*S]) + o_lo (bf16 [B*S, H]): training forward for attention_bwd_sp (clibd_attention_fwd_save)."""
+    lse (fp32 [B*nheads*S]) + o_lo (bf16 [B*S, H]): the saving forward, for attention_bwd_sp."""
     _chk(qkv, BF16, "qkv")
-    if lse is not None or o_lo is not None:
-        _chk(out, BF16, "out"); _chk(lse, F32, "lse"); _chk(o_lo, BF16, "o_lo")
-        H_ = nheads * 64
-        if (nq is not None and nq != S) or out_fp8_scale > 0 or tuple(qkv.shape) != (B * S, 3 * H_) or tuple(out.shape) != (B * S, H_) \
-                or tuple(o_lo.shape) != (B * S, H_) or lse.numel() != B * nheads * S:
-            raise ValueError("attention_fwd: the saving form needs nq = S, bf16 out [B*S,H], o_lo [B*S,H], lse [B*nheads*S]")
-        if key_mask is not None:
-            _chk(key_mask, I32, "key_mask")
-        d = drop if (drop is not None and drop.thr16 > 0) else Drop(0.0, 0)
-        check(_lib.load().clibd_attention_fwd_save(qkv.data_ptr(), B, S, nheads, _p(key_mask), out.data_ptr(), d.seed, d.thr16, d.scale,
-                                                   lse.data_ptr(), o_lo.data_ptr(), _stream()), "attention_fwd_save")
-        return
-    _chk(out, FP8 if out_fp8_scale > 0 else BF16, "out")
     H = nheads * 64
     nq = S if nq is None else nq
+    if lse is not None or o_lo is not None:
+        _chk(lse, F32, "lse"); _chk(o_lo, BF16, "o_lo")
+        if nq != S or out_fp8_scale > 0 or tuple(o_lo.shape) != (B * S, H) or lse.numel() != B * nheads * S:
+            raise ValueError("attention_fwd: the saving form needs nq = S, bf16 out [B*S,H], o_lo [B*S,H], lse [B*nheads*S]")
+    _chk(out, FP8 if out_fp8_scale > 0 else BF16, "out")
     if tuple(qkv.shape) != (B * S, 3 * H) or tuple(out.shape) != (B * nq, H):
         raise ValueError("attention_fwd: qkv must be [B*S,3H], out [B*nq,H] with H = 64*nheads")
     if key_mask is not None:
         _chk(key_mask, I32, "key_mask")
         if tuple(key_mask.shape) != (B, S):
             raise ValueError("attention_fwd: key_mask must be [B,S]")
-    if out_fp8_scale > 0:
-        d = drop if (drop is not None and drop.thr16 > 0) else Drop(0.0, 0)
-        check(_lib.load().clibd_attention_fwd_fp8(qkv.data_ptr(), B, S, nheads, _p(key_mask), out.data_ptr(), nq, nq, d.seed, d.thr16, d.scale,
-                                                  float(out_fp8_scale), _stream()), "attention_fwd_fp8")
-        return
-    if drop is not None and drop.thr16 > 0:
-        check(_lib.load().clibd_attention_fwd_drop(qkv.data_ptr(), B, S, nheads, _p(key_mask), out.data_ptr(), nq, nq, drop.seed, drop.thr16,
-                                                   drop.scale, _stream()), "attention_fwd_drop")
-        return
-    check(_lib.load().clibd_attention_fwd(qkv.data_ptr(), B, S, nheads, _p(key_mask), out.data_ptr(), nq, nq, _stream()), "attention_fwd")
+    check(_lib.load().clibd_attention_fwd(qkv.data_ptr(), B, S, nheads, _p(key_mask), out.data_ptr(), nq, nq, *_drop_args(drop),
+                                          float(out_fp8_scale), _p(lse), _p(o_lo), _stream()), "attention_fwd")
 
 
 def attention_bwd(qkv, dout, B, S, nheads, key_mask, dqkv, nq: Optional[int] = None, drop=None) -> None:
@@ -635,12 +511,8 @@ def attention_bwd(qkv, dout, B, S, nheads, key_mask, dqkv, nq: Optional[int] = N
         raise ValueError("attention_bwd: shapes")
     if key_mask is not None:
         _chk(key_mask, I32, "key_mask")
-    if drop is not None and drop.thr16 > 0:
-        check(_lib.load().clibd_attention_bwd_drop(qkv.data_ptr(), dout.data_ptr(), B, S, nheads, _p(key_mask), dqkv.data_ptr(), nq, nq,
-                                                   drop.seed, drop.thr16, drop.scale, _stream()), "attention_bwd_drop")
-        return
-    check(_lib.load().clibd_attention_bwd(qkv.data_ptr(), dout.data_ptr(), B, S, nheads, _p(key_mask), dqkv.data_ptr(), nq, nq, _stream()),
-          "attention_bwd")
+    check(_lib.load().clibd_attention_bwd(qkv.data_ptr(), dout.data_ptr(), B, S, nheads, _p(key_mask), dqkv.data_ptr(), nq, nq,
+                                          *_drop_args(drop), _stream()), "attention_bwd")
 
 
 def attention_bwd_sp(qkv, dout, out, o_lo, lse, B, S, nheads, dqkv, drop=None) -> None:
@@ -655,9 +527,8 @@ def attention_bwd_sp(qkv, dout, out, o_lo, lse, B, S, nheads, dqkv, drop=None) -
     _chk(lse, F32, "lse")
     if lse.numel() != B * nheads * S:
         raise ValueError("attention_bwd_sp: lse must have B*nheads*S elements")
-    d = drop if (drop is not None and drop.thr16 > 0) else Drop(0.0, 0)
     check(_lib.load().clibd_attention_bwd_sp(qkv.data_ptr(), dout.data_ptr(), out.data_ptr(), o_lo.data_ptr(), lse.data_ptr(), B, S, nheads,
-                                             dqkv.data_ptr(), d.seed, d.thr16, d.scale, _stream()), "attention_bwd_sp")
+                                             dqkv.data_ptr(), *_drop_args(drop), _stream()), "attention_bwd_sp")
 
 
 def lora_pack(a_q, a_v, b_q, b_v, v_fwd, v_bwd, a_cat, w_dt) -> None:
@@ -1152,16 +1023,16 @@ def layernorm_param_grads(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor
     M, H = x.shape
     if tuple(dy.shape) != (M, H) or stats.numel() != 2 * M or dgamma.numel() != H or dbeta.numel() != H:
         raise ValueError("layernorm_param_grads: shape mismatch")
-    d = drop if drop is not None else Drop(0.0, 0)
+    d = _drop_args(drop)
     if ordered:
         lib = _lib.load()
         ws = _ordered_workspace("ln_param", int(lib.clibd_layernorm_param_grads_workspace_bytes(M, H)), x.device)
         check(lib.clibd_layernorm_param_grads_ordered(dy.data_ptr(), int(dy.dtype == F32), _rowmajor(dy, "dy"), x.data_ptr(), stats.data_ptr(), M, H,
-                                                      dgamma.data_ptr(), dbeta.data_ptr(), d.seed, d.thr16, d.scale, ws.data_ptr(), ws.numel(), _stream()),
+                                                      dgamma.data_ptr(), dbeta.data_ptr(), *d, ws.data_ptr(), ws.numel(), _stream()),
               "layernorm_param_grads_ordered")
         return
     check(_lib.load().clibd_layernorm_param_grads(dy.data_ptr(), int(dy.dtype == F32), _rowmajor(dy, "dy"), x.data_ptr(), stats.data_ptr(), M, H,
-                                                  dgamma.data_ptr(), dbeta.data_ptr(), d.seed, d.thr16, d.scale, _stream()), "layernorm_param_grads")
+                                                  dgamma.data_ptr(), dbeta.data_ptr(), *d, _stream()), "layernorm_param_grads")
 
 
 def batch_sum(x: torch.Tensor, out: torch.Tensor, ordered: bool = False) -> None:

@@ -138,7 +138,7 @@ int clibd_quantize_rows_fp8(const float* w, int N, int K, float act_scale, void*
  * nn.Linear (the backward of the same call sites as clibd_gemm_bf16_nt: timm Mlp.fc1 / fc2, Attention.proj, image_encoder.py:106-107; HF
  * BertIntermediate / BertOutput / BertSelfOutput .dense, dna_encoder.py:137) on e4m3 operands.
  *   A [M,K]  = the gradient dY as e4m3 bytes with ONE power-of-two scale per row: A[m,k] = e4m3(dY[m,k] * s_m), a_row_dequant[m] = 1 / s_m
- *              (fp32 [M]; written by clibd_layernorm_bwd_fp8, or inherited from the form below);
+ *              (fp32 [M]; written by clibd_layernorm_bwd with dx_fp8, or inherited from the form below);
  *   W [N,K]  = the TRANSPOSED weight (row n = input channel n of the layer) as clibd_quantize_rows_fp8_bf16 writes it, col_scale[n] its
  *              row's dequantisation factor (times 1 / out_fp8_scale of the producer when A came from the third form).
  * Forms (bias-free, no adapters; M % 4 == 0, N % 256 == 0, K % 256 == 0, K >= 512; lda, ldw, K in bytes):
@@ -150,7 +150,7 @@ int clibd_quantize_rows_fp8(const float* w, int N, int K, float act_scale, void*
  *                             (> 0 exactly for this form) is a power of two <= 448 / (256 * 1.13 * l1max) with l1max from
  *                             clibd_quantize_rows_fp8_bf16, so that no value saturates (|gelu'| <= 1.13, scaled row maxima < 256).
  *                             ABI 5: with ep->out_pre_bf16 (+ ld_pre, and a_row_dequant, whose values must be powers of two as
- *                             clibd_layernorm_bwd_fp8 writes them) the form ALSO writes out_pre_bf16[m,n] = bf16(acc * col_scale[n] * aux[m,n] *
+ *                             clibd_layernorm_bwd writes them) the form ALSO writes out_pre_bf16[m,n] = bf16(acc * col_scale[n] * aux[m,n] *
  *                             a_row_dequant[m]), the true d(fc1 out): under full fine-tuning (trainable base weights) the bf16 weight
  *                             gradient of fc1 contracts it with the layer input while the next dgrad takes the e4m3 bytes. */
 int clibd_gemm_fp8_dgrad_nt(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* col_scale,
@@ -189,65 +189,46 @@ int clibd_cast_transpose_f32_to_bf16(const float* in, int R, int C, void* out, v
  * (reference: linear_a_q/linear_a_v image_encoder.py:41-42, w_a dna_encoder.py:76) emitted as bf16 [M,8].
  * H % 64 == 0, H <= 1024.
  * ------------------------------------------------------------------------------------------------ */
-int clibd_layernorm_fwd(const float* x, int M, int H, const float* gamma, const float* beta, float eps,
-                        void* y_bf16, float* y_f32, float* stats, const void* lora_a_bf16, void* t_bf16,
-                        void* stream);
 /* Dropout (HF BERT train mode, p = 0.1: BertEmbeddings.dropout, BertSelfOutput.dropout, BertOutput.dropout,
  * BertSelfAttention.dropout on the probabilities).  Masks are a pure function of (seed, element index) — lowbias32 hash of
  * (index >> 1) ^ seed, 16 bits per element, keep iff bits >= round(p*65536) — so nothing is stored and the backward
  * recomputes them.  Element index: row*H + col for [M,H] activations; ((b*heads+h)*S + q)*256 + key for attention.
- * _drop variants: y = dropout(LN(x)) (embeddings);  backward: the bf16 output only is masked (it is the gradient that
- * enters the dgrad GEMM of the dropped dense output; the fp32 output is the residual-path gradient). */
-/* fp8-forward mode: additionally (or only: y_bf16 / y_f32 may both be NULL) y_fp8[m,c] = e4m3(y * fp8_scale), saturating
- * at +-448 — the operand of the next clibd_gemm_fp8_nt.  The LoRA down-projection still reads bf16(y). */
-int clibd_layernorm_fwd_fp8(const float* x, int M, int H, const float* gamma, const float* beta, float eps,
-                            void* y_bf16, float* y_f32, float* stats, const void* lora_a_bf16, void* t_bf16,
-                            uint32_t drop_seed, int drop_thr16, float drop_scale, void* y_fp8, float fp8_scale, void* stream);
-int clibd_layernorm_fwd_drop(const float* x, int M, int H, const float* gamma, const float* beta, float eps,
-                             void* y_bf16, float* y_f32, float* stats, const void* lora_a_bf16, void* t_bf16,
-                             uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream);
-/* dx = LN'(dy) [+ dres]; dy is bf16 (dy_bf16) or fp32 (dy_f32), exactly one non-null.
- * Outputs dx_f32 and/or dx_bf16. gamma is frozen on the LoRA path, so no dgamma/dbeta here. */
-int clibd_layernorm_bwd(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats,
-                        const float* gamma, int M, int H, const float* dres_f32, float* dx_f32,
-                        void* dx_bf16, void* stream);
-int clibd_layernorm_bwd_drop(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats,
-                             const float* gamma, int M, int H, const float* dres_f32, float* dx_f32,
-                             void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream);
-/* The same backward with the RESIDUAL GRADIENT carried in bf16 (frozen-base / LoRA mode): dx = LN'(dy) [+ dres_bf16];
- * dx_res_bf16 (optional) = bf16(dx), the gradient of the residual sum handed to the next block; dx_bf16 (optional) = bf16(dx x the
- * dense branch's dropout mask) when drop_thr16 > 0, else the same values.  10 instead of 16 bytes per element of a pre-LN block
- * (the reference's autograd keeps this stream in fp32: the rounding it adds is budgeted in DESIGN.md §4). */
-int clibd_layernorm_bwd_res16(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
-                              int M, int H, const void* dres_bf16, void* dx_res_bf16, void* dx_bf16, uint32_t drop_seed,
-                              int drop_thr16, float drop_scale, void* stream);
-/* The general form (round 4; full fine-tune on the bf16 residual-gradient stream): every optional operand of the three entry
- * points above in one call — residual gradient in fp32 (dres_f32) OR bf16 (dres_bf16), outputs dx_f32 / dx_res_bf16 / dx_bf16
- * (at least one), dropout on the dx_bf16 copy, and dgamma / dbeta (both or neither; accumulated).  Same kernel, same arithmetic. */
-int clibd_layernorm_bwd_any(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
-                            int M, int H, const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16,
-                            void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, float* dgamma, float* dbeta,
-                            void* stream);
-/* 8-bit dgrad (ABI 4): clibd_layernorm_bwd_any without parameter gradients, and additionally the copy the dense branch's dgrad consumes
- * (dropout mask applied, as dx_bf16 — which may now be NULL) as e4m3 bytes with one power-of-two scale per row:
- *   s_m = 2^(7 - floor(log2 max_c |v[m,c]|))  (1 for an all-zero row),  dx_fp8[m,c] = e4m3(v[m,c] * s_m),  row_dequant[m] = 1 / s_m.
- * dx_fp8 uint8 [M,H], row_dequant fp32 [M]: the A operand of clibd_gemm_fp8_dgrad_nt. */
-int clibd_layernorm_bwd_fp8(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
-                            int M, int H, const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16,
-                            void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* dx_fp8, float* row_dequant,
-                            void* stream);
-/* ABI 5 — the same with the LayerNorm parameter gradients (dgamma[c] += sum_rows dy xhat, dbeta[c] += sum_rows dy, as clibd_layernorm_bwd_pg):
- * the 8-bit dgrad under full fine-tuning (model_config.disable_lora, the reference's final BIOSCAN-1M / 5M recipe): the dgrad takes the e4m3
- * rows, the bf16 weight gradient takes dx_bf16, both written in this one pass. */
-int clibd_layernorm_bwd_fp8_pg(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
-                               int M, int H, const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16,
-                               void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* dx_fp8, float* row_dequant,
-                               float* dgamma, float* dbeta, void* stream);
-/* full fine-tune mode: the same backward that also accumulates the parameter gradients it has the operands for
- *   dgamma[c] += sum_m dy[m,c] * xhat[m,c],  dbeta[c] += sum_m dy[m,c]     (fp32 [H], caller zeroes once per step). */
-int clibd_layernorm_bwd_pg(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
-                           int M, int H, const float* dres_f32, float* dx_f32, void* dx_bf16, uint32_t drop_seed, int drop_thr16,
-                           float drop_scale, float* dgamma, float* dbeta, void* stream);
+ * drop_thr16 = round(p * 65536) (0: no dropout, seed and scale ignored), drop_scale = 1 / (1 - p). */
+/* Forward.  Outputs y_bf16 / y_f32 / y_fp8: at least one.  Optional arguments are NULL / 0 when unused:
+ *   stats                : the saved (mean, rstd) of the backward;
+ *   lora_a_bf16 + t_bf16 : together or both NULL: the adapters' down-projection of bf16(y);
+ *   drop_thr16 > 0       : y = dropout(LN(x)) on every output (embeddings);
+ *   y_fp8 (+ fp8_scale > 0; 4-byte aligned): fp8-forward mode, additionally (or only) y_fp8[m,c] = e4m3(y * fp8_scale), saturating
+ *                          at +-448 — the operand of the next clibd_gemm_fp8_nt.  The LoRA down-projection still reads bf16(y).
+ *                          y_fp8 == NULL: no e4m3 output, fp8_scale ignored. */
+int clibd_layernorm_fwd(const float* x, int M, int H, const float* gamma, const float* beta, float eps,
+                        void* y_bf16, float* y_f32, float* stats, const void* lora_a_bf16, void* t_bf16,
+                        uint32_t drop_seed, int drop_thr16, float drop_scale, void* y_fp8, float fp8_scale, void* stream);
+/* Backward.  dx = LN'(dy) [+ dres]; dy is bf16 (dy_bf16) or fp32 (dy_f32), exactly one non-null.  One kernel family, the same
+ * arithmetic in every form; the optional arguments (NULL / 0 when unused) select what is read and written:
+ *   dres_f32 | dres_bf16 : the residual gradient added to dx, in fp32 or in bf16 (frozen-base / LoRA mode), at most one.  The bf16
+ *                          stream costs 10 instead of 16 bytes per element of a pre-LN block (the reference's autograd keeps this
+ *                          stream in fp32: the rounding it adds is budgeted in DESIGN.md §4);
+ *   outputs, at least one: dx_f32; dx_res_bf16 = bf16(dx), the gradient of the residual sum handed to the next block; dx_bf16 =
+ *                          bf16(dx x the dense branch's dropout mask) when drop_thr16 > 0, else the same values (the masked copy is the
+ *                          gradient that enters the dgrad GEMM of the dropped dense output; the others are the residual-path gradient);
+ *   dx_fp8 + row_dequant : together or both NULL (8-bit dgrad): the copy the dense branch's dgrad consumes (dropout mask applied, as
+ *                          dx_bf16) as e4m3 bytes with one power-of-two scale per row:
+ *                            s_m = 2^(7 - floor(log2 max_c |v[m,c]|))  (1 for an all-zero row),  dx_fp8[m,c] = e4m3(v[m,c] * s_m),
+ *                            row_dequant[m] = 1 / s_m.
+ *                          dx_fp8 uint8 [M,H] (4-byte aligned), row_dequant fp32 [M]: the A operand of clibd_gemm_fp8_dgrad_nt;
+ *   dgamma + dbeta       : together or both NULL (full fine-tune mode, model_config.disable_lora; gamma is frozen on the LoRA path): the
+ *                          parameter gradients the pass has the operands for, ACCUMULATED,
+ *                            dgamma[c] += sum_m dy[m,c] * xhat[m,c],  dbeta[c] += sum_m dy[m,c]   (fp32 [H], caller zeroes once per step);
+ *                          with dx_fp8 the dgrad takes the e4m3 rows and the bf16 weight gradient takes dx_bf16, both from this one pass;
+ *   workspace            : needs dgamma / dbeta.  NULL (workspace_bytes 0): float atomics.  Else (deterministic mode; 16-byte aligned,
+ *                          workspace_bytes >= clibd_layernorm_bwd_pg_workspace_bytes(M, H)): every block writes its partial sums there
+ *                          and a second kernel adds them in block order, so dgamma / dbeta repeat bit for bit. */
+size_t clibd_layernorm_bwd_pg_workspace_bytes(int M, int H);
+int clibd_layernorm_bwd(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma, int M, int H,
+                        const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16, void* dx_bf16,
+                        uint32_t drop_seed, int drop_thr16, float drop_scale, void* dx_fp8, float* row_dequant,
+                        float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K3: multi-head attention, head dim 64, whole sequence per workgroup (S <= 256: ViT 197, BarcodeBERT 133,
@@ -260,10 +241,17 @@ int clibd_layernorm_bwd_pg(const void* dy_bf16, const float* dy_f32, const float
  * timm pools token 0).  out / dout hold `out_seq` (>= nq) rows per sequence: row (b*out_seq + q).  The backward writes
  * the full dqkv [B*S,3H]: dq of rows >= nq is zero, dk/dv collect the active queries only.
  * ------------------------------------------------------------------------------------------------ */
-int clibd_attention_fwd(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out,
-                        int nq, int out_seq, void* stream);
-int clibd_attention_bwd(const void* qkv, const void* dout, int B, int S, int nheads, const int32_t* key_mask,
-                        void* dqkv, int nq, int dout_seq, void* stream);
+/* Forward.  drop_thr16 > 0: dropout on the attention probabilities (mask definition: see clibd_layernorm_fwd).
+ * out_fp8_scale == 0: bf16 out.  out_fp8_scale > 0 (fp8-forward mode): out leaves as e4m3(o * out_fp8_scale) bytes [B*out_seq, H]
+ * (operand of the projection clibd_gemm_fp8_nt; the backward recomputes what it needs from qkv, so no bf16 copy is kept).
+ * lse + o_lo (together or both NULL; nq = out_seq = S, bf16 out, o_lo 16-byte aligned): the saving forward of the single-pass
+ * backward below. */
+int clibd_attention_fwd(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out, int nq, int out_seq,
+                        uint32_t drop_seed, int drop_thr16, float drop_scale, float out_fp8_scale, float* lse, void* o_lo,
+                        void* stream);
+/* Two-phase backward: recomputes the probabilities (and the forward's dropout mask, from the same seed / thr16 / scale) from qkv. */
+int clibd_attention_bwd(const void* qkv, const void* dout, int B, int S, int nheads, const int32_t* key_mask, void* dqkv,
+                        int nq, int dout_seq, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream);
 
 /* Single-pass backward (frozen-base training, full sequences): the forward also saves, per (head, query), the log2-domain
  * log-sum-exp of the un-dropped scores — lse fp32 [B * nheads, S] — and the bf16 residual of its output rounding — o_lo bf16
@@ -271,22 +259,9 @@ int clibd_attention_bwd(const void* qkv, const void* dout, int B, int S, int nhe
  *   P = exp2(c2 s - lse), delta = dO . (out + o_lo), dS = P o (dP - delta), dV += P^T dO, dK += dS^T Q, dQ += dS K
  * (one 8-wave workgroup per head, K / V / Q / dO resident in LDS, dK / dV in the key-owning wave's accumulators, dQ from a dS
  * exchange through LDS: no atomics, deterministic).  Same results as clibd_attention_bwd up to rounding points.
- * clibd_attention_fwd_save: nq = S; key_mask allowed in the forward.  clibd_attention_bwd_sp: no key mask, S <= 224. */
-int clibd_attention_fwd_save(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out, uint32_t drop_seed,
-                             int drop_thr16, float drop_scale, float* lse, void* o_lo, void* stream);
+ * clibd_attention_fwd with lse / o_lo: nq = S; key_mask allowed in the forward.  clibd_attention_bwd_sp: no key mask, S <= 224. */
 int clibd_attention_bwd_sp(const void* qkv, const void* dout, const void* out, const void* o_lo, const float* lse, int B, int S,
                            int nheads, void* dqkv, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream);
-/* fp8-forward mode: the attention output leaves as e4m3(o * out_fp8_scale) bytes [B*out_seq, H] (operand of the projection
- * clibd_gemm_fp8_nt; the backward recomputes what it needs from qkv, so no bf16 copy is kept). */
-int clibd_attention_fwd_fp8(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out_fp8,
-                            int nq, int out_seq, uint32_t drop_seed, int drop_thr16, float drop_scale, float out_fp8_scale,
-                            void* stream);
-/* same with dropout on the attention probabilities (see clibd_layernorm_fwd_drop for the mask definition) */
-int clibd_attention_fwd_drop(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out,
-                             int nq, int out_seq, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream);
-int clibd_attention_bwd_drop(const void* qkv, const void* dout, int B, int S, int nheads, const int32_t* key_mask,
-                             void* dqkv, int nq, int dout_seq, uint32_t drop_seed, int drop_thr16, float drop_scale,
-                             void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K6: LoRA (rank 4 on q and v; reference image_encoder.py:13-46, dna_encoder.py:68-77,
@@ -554,13 +529,7 @@ int clibd_slice_rows_cast_bf16(const float* x, int B, int S, int H, int s0, int 
  * a caller-owned workspace (size from its *_workspace_bytes query; 16-byte aligned) and a second kernel adds the partials in a fixed order
  * (block, slice, chunk order), so that the result depends on the inputs and the shape only and repeats bit for bit.  Outputs ACCUMULATE as
  * in the atomic forms; nothing allocates; everything is enqueued on `stream`.  A null or short workspace returns -1. */
-/* clibd_layernorm_bwd_any / clibd_layernorm_bwd_fp8_pg with the parameter gradients summed in block order (dgamma, dbeta required;
- * dx_fp8 / row_dequant optional, together). */
-size_t clibd_layernorm_bwd_pg_workspace_bytes(int M, int H);
-int clibd_layernorm_bwd_pg_ordered(const void* dy_bf16, const float* dy_f32, const float* x, const float* stats, const float* gamma,
-                                   int M, int H, const float* dres_f32, const void* dres_bf16, float* dx_f32, void* dx_res_bf16,
-                                   void* dx_bf16, uint32_t drop_seed, int drop_thr16, float drop_scale, void* dx_fp8, float* row_dequant,
-                                   float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+/* (clibd_layernorm_bwd takes its workspace as an argument: declared with the LayerNorm entry points above.) */
 size_t clibd_layernorm_param_grads_workspace_bytes(int M, int H);
 int clibd_layernorm_param_grads_ordered(const void* dy, int dy_is_f32, int ld_dy, const float* x, const float* stats, int M, int H,
                                         float* dgamma, float* dbeta, uint32_t drop_seed, int drop_thr16, float drop_scale,

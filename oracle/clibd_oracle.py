@@ -82,7 +82,7 @@ _DGRAD8 = False
 @contextlib.contextmanager
 def dgrad8(on: bool = True):
     """bf16 / fp8 modes: the activation-gradient products of attention projection, fc1 and fc2 of every layer evaluated as the kernels'
-    8-bit dgrad (clibd_amd.engine numerics dgrad="fp8", include/clibd_hip.h clibd_gemm_fp8_dgrad_nt / clibd_layernorm_bwd_fp8):
+    8-bit dgrad (clibd_amd.engine numerics dgrad="fp8", include/clibd_hip.h clibd_gemm_fp8_dgrad_nt / clibd_layernorm_bwd with dx_fp8):
       gradient rows  : e4m3(g[m,:] * s_m), s_m = 2^(7 - floor(log2 max|g[m,:]|)) taken from the fp32 gradient (1 for a zero row);
       d(fc1 out)     : e4m3(value * s_m * c2) with the s_m of the fc2 dgrad's operand rows and the per-layer constant
                        c2 = 2^floor(log2(448 / (256 * 1.13 * l1max))), l1max the largest row l1 norm of the quantised fc2^T image;

@@ -39,7 +39,7 @@ def test_python_binding_covers_every_declared_symbol(lib):
     from clibd_amd import _lib
 
     assert sorted(_lib.SIGNATURES) == declared_symbols()
-    assert _lib.load().clibd_abi_version() == _lib.ABI_VERSION == 5
+    assert _lib.load().clibd_abi_version() == _lib.ABI_VERSION == 6
 
 
 def test_binding_refuses_a_library_built_from_other_sources(lib, monkeypatch):
@@ -71,7 +71,7 @@ def test_host_side_validation_needs_no_gpu(lib):
     ep = _lib.GemmEpilogue()
     assert L.clibd_gemm_bf16_nt(None, 64, None, 64, 8, 16, 64, ctypes.byref(ep), None) == -1
     assert b"null" in L.clibd_last_error()
-    assert L.clibd_attention_fwd(ctypes.c_void_p(16), 1, 300, 1, None, ctypes.c_void_p(16), 300, 300, None) == -1
+    assert L.clibd_attention_fwd(ctypes.c_void_p(16), 1, 300, 1, None, ctypes.c_void_p(16), 300, 300, 0, 0, 1.0, 0.0, None, None, None) == -1
     assert L.clibd_softce_workspace_bytes(32, 32, 768) > 32 * 32 * 4
     # round 6: the stream-K tail plan (256 CUs assumed without a device): 591 tiles = 2 rounds + 79 -> 3 K-slices; 399 tiles (tail 143) and K = 768: none
     assert L.clibd_gemm_tail_workspace_bytes(50432, 768, 3072) == 1024 + 79 * 2 * 256 * 256 * 4
@@ -79,6 +79,40 @@ def test_host_side_validation_needs_no_gpu(lib):
     assert L.clibd_gemm_tail_workspace_bytes(34048, 768, 3072) == 0 and L.clibd_gemm_tail_workspace_bytes(50432, 3072, 768) == 0
     assert L.clibd_gemm_tail_workspace_bytes(403456, 768, 3072) == 1024 + 120 * 1 * 256 * 256 * 4      # the metric's batch: 4 728 tiles = 18 rounds + 120 -> 2 slices
     assert L.clibd_gemm_tail_workspace_bytes(403456, 768, 3072) <= 48 * 1024 * 1024 + 1024
+
+
+def test_layernorm_and_attention_argument_combinations_are_validated_on_the_host(lib):
+    """The optional arguments of the one-entry-point-per-operation forms: every inconsistent combination is rejected before a launch."""
+    from clibd_amd import _lib
+
+    L = _lib.load()
+    p = ctypes.c_void_p(256)   # never dereferenced
+    ws = L.clibd_layernorm_bwd_pg_workspace_bytes(64, 768)
+
+    def ln_bwd(dres_f32=None, dres_bf16=None, dx_f32=None, dx_res=None, dx_bf16=None, dx_fp8=None, row_dequant=None, dgamma=None, dbeta=None,
+               workspace=None, workspace_bytes=0):
+        return L.clibd_layernorm_bwd(p, None, p, p, p, 64, 768, dres_f32, dres_bf16, dx_f32, dx_res, dx_bf16, 0, 0, 1.0, dx_fp8, row_dequant,
+                                     dgamma, dbeta, workspace, workspace_bytes, None)
+
+    assert ln_bwd(dx_bf16=p, dx_fp8=p) == -1 and b"row_dequant" in L.clibd_last_error()
+    assert ln_bwd(dx_bf16=p, dgamma=p) == -1 and b"dbeta" in L.clibd_last_error()
+    assert ln_bwd(dx_bf16=p, dres_f32=p, dres_bf16=p) == -1 and b"either fp32 or bf16" in L.clibd_last_error()
+    assert ln_bwd(dx_bf16=p, workspace=p, workspace_bytes=ws) == -1 and b"workspace" in L.clibd_last_error()
+    assert ln_bwd() == -1 and b"no output" in L.clibd_last_error()
+
+    def ln_fwd(y_bf16=None, lora_a=None, t=None, y_fp8=None, fp8_scale=0.0):
+        return L.clibd_layernorm_fwd(p, 64, 768, p, p, 1e-6, y_bf16, None, None, lora_a, t, 0, 0, 1.0, y_fp8, fp8_scale, None)
+
+    assert ln_fwd(y_fp8=p, fp8_scale=0.0) == -1 and b"positive scale" in L.clibd_last_error()
+    assert ln_fwd(y_bf16=p, lora_a=p) == -1 and b"lora_a/t" in L.clibd_last_error()
+
+    def att_fwd(nq=64, out_seq=64, out_fp8_scale=0.0, lse=None, o_lo=None):
+        return L.clibd_attention_fwd(p, 2, 64, 2, None, p, nq, out_seq, 0, 0, 1.0, out_fp8_scale, lse, o_lo, None)
+
+    assert att_fwd(lse=p) == -1 and b"together" in L.clibd_last_error()
+    assert att_fwd(nq=32, lse=p, o_lo=p) == -1 and b"nq = out_seq = S" in L.clibd_last_error()
+    assert att_fwd(out_fp8_scale=2.0, lse=p, o_lo=p) == -1 and b"bf16 out" in L.clibd_last_error()
+    assert att_fwd(out_fp8_scale=-1.0) == -1 and b"fp8 scale" in L.clibd_last_error()
 
 
 def test_product_path_has_no_cpu_fallback():

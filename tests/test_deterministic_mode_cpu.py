@@ -8,7 +8,7 @@ import pytest
 import torch
 
 ROOT = Path(__file__).resolve().parents[1]
-NEW = ["clibd_layernorm_bwd_pg_workspace_bytes", "clibd_layernorm_bwd_pg_ordered", "clibd_layernorm_param_grads_workspace_bytes",
+NEW = ["clibd_layernorm_bwd_pg_workspace_bytes", "clibd_layernorm_bwd", "clibd_layernorm_param_grads_workspace_bytes",
        "clibd_layernorm_param_grads_ordered", "clibd_batch_sum_workspace_bytes", "clibd_batch_sum_f32_ordered",
        "clibd_bert_embed_bwd_workspace_bytes", "clibd_bert_embed_bwd_ordered", "clibd_colsum_workspace_bytes", "clibd_colsum_bf16_ordered",
        "clibd_gemm_tn_colsum_workspace_bytes", "clibd_gemm_bf16_tn_splitk_ordered"]
@@ -29,7 +29,7 @@ def test_header_declares_and_library_exports_the_ordered_forms(L):
     declared = set(re.findall(r"\b(clibd_[a-z0-9_]+)\s*\(", text))
     for name in NEW:
         assert name in declared and name in _lib.SIGNATURES and hasattr(L, name), name
-    assert _lib.ABI_VERSION == 5 and L.clibd_abi_version() == 5
+    assert _lib.ABI_VERSION == 6 and L.clibd_abi_version() == 6
 
 
 def test_workspace_queries(L):
@@ -55,10 +55,10 @@ def test_workspace_queries(L):
 
 def test_host_side_validation_rejects_missing_or_short_workspaces(L):
     p = ctypes.c_void_p(256)   # never dereferenced: every call below is rejected before a launch
-    assert L.clibd_layernorm_bwd_pg_ordered(p, None, p, p, p, 64, 768, None, None, None, None, p, 0, 0, 1.0, None, None, p, p, None, 0, None) == -1
+    assert L.clibd_layernorm_bwd(p, None, p, p, p, 64, 768, None, None, None, None, p, 0, 0, 1.0, None, None, p, p, None, 16, None) == -1   # a size without a workspace
     assert b"workspace" in L.clibd_last_error()
     short = L.clibd_layernorm_bwd_pg_workspace_bytes(64, 768) - 16
-    assert L.clibd_layernorm_bwd_pg_ordered(p, None, p, p, p, 64, 768, None, None, None, None, p, 0, 0, 1.0, None, None, p, p, p, short, None) == -1
+    assert L.clibd_layernorm_bwd(p, None, p, p, p, 64, 768, None, None, None, None, p, 0, 0, 1.0, None, None, p, p, p, short, None) == -1
     assert b"too small" in L.clibd_last_error()
     assert L.clibd_batch_sum_f32_ordered(p, 2048, 768, p, p, 16, None) == -1
     assert L.clibd_colsum_bf16_ordered(p, 768, 1000, 768, p, None, 0, None) == -1

@@ -15,7 +15,7 @@ def ints(shape, lo, hi, g):
 
 
 def row_scale(v):
-    """s_m = 2^(7 - floor(log2 max|row|)), 1 for an all-zero row (clibd_layernorm_bwd_fp8)."""
+    """s_m = 2^(7 - floor(log2 max|row|)), 1 for an all-zero row (the dx_fp8 rows of clibd_layernorm_bwd)."""
     amax = v.abs().amax(dim=1, keepdim=True)
     e = torch.floor(torch.log2(torch.where(amax > 0, amax, torch.ones_like(amax))))
     return torch.where(amax > 0, torch.exp2(7.0 - e), torch.ones_like(amax))
@@ -156,7 +156,7 @@ def test_layernorm_bwd_fp8_two_row_form_equals_the_one_row_form(dev):
 
 
 def test_layernorm_bwd_fp8_with_parameter_gradients(dev):
-    """clibd_layernorm_bwd_fp8_pg (8-bit dgrad under full fine-tune): the e4m3 rows / scales / bf16 copies of the plain fp8 call, bit for
+    """clibd_layernorm_bwd with dx_fp8 and dgamma / dbeta (8-bit dgrad under full fine-tune): the e4m3 rows / scales / bf16 copies of the plain fp8 call, bit for
     bit, plus the parameter gradients of the bf16 path's call (float-atomic order only)."""
     from clibd_amd import ops
 

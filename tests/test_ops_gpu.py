@@ -236,7 +236,7 @@ def test_attention_fwd_bwd(ops, dev, B, S, nh, masked):
 @pytest.mark.parametrize("B,S,nh,p_drop", [(2, 197, 2, 0.0), (3, 133, 3, 0.1), (2, 224, 1, 0.0), (5, 20, 2, 0.0), (1, 7, 1, 0.1), (2, 100, 12, 0.0),
                                             (40, 197, 12, 0.0)])
 def test_attention_single_pass_backward(ops, dev, B, S, nh, p_drop):
-    """clibd_attention_fwd_save + clibd_attention_bwd_sp: the training forward also writes the log-sum-exp and the rounding
+    """clibd_attention_fwd with lse / o_lo + clibd_attention_bwd_sp: the training forward also writes the log-sum-exp and the rounding
     residual of its output (out unchanged, bit for bit), and the single-pass backward built on them must give the gradients of
     the fp64 statement (same gate as the two-phase kernel) and agree with the two-phase kernel — under dropout too, where both
     evaluate the same counter-based masks.  B x heads >= 2 x CUs at S = 197 takes the persistent forward."""
@@ -1138,7 +1138,7 @@ def test_transpose_with_column_sums(ops, dev, R, C, ld_extra):
 @pytest.mark.parametrize("M,H,f32dy,drop,res", [(300, 768, False, False, True), (5000, 768, True, True, False), (133, 512, True, False, False),
                                                 (64, 1024, False, False, True)])
 def test_layernorm_bwd_with_fused_param_grads(ops, dev, M, H, f32dy, drop, res):
-    """clibd_layernorm_bwd_pg = clibd_layernorm_bwd (bit-identical dx) + d(gamma), d(beta) accumulated in the same pass."""
+    """clibd_layernorm_bwd with dgamma / dbeta = the call without them (bit-identical dx) + d(gamma), d(beta) accumulated in the same pass."""
     g = torch.Generator().manual_seed(M + H)
     x = torch.randn(M, H, generator=g) * 2 + 0.3
     gam, bet = torch.randn(H, generator=g), torch.randn(H, generator=g)
@@ -1168,7 +1168,7 @@ def test_layernorm_bwd_with_fused_param_grads(ops, dev, M, H, f32dy, drop, res):
 # ----------------------------------------------------------------------------------------------- round 3: bf16 residual-gradient stream
 @pytest.mark.parametrize("M,H,f32dy,drop", [(1000, 768, False, False), (333, 768, True, True), (70, 512, False, True), (64, 1024, True, False)])
 def test_layernorm_bwd_bf16_residual_stream(ops, dev, M, H, f32dy, drop):
-    """clibd_layernorm_bwd_res16 = clibd_layernorm_bwd with the residual gradient read and written as bf16: fed the bf16
+    """clibd_layernorm_bwd with dres_bf16 / dx_res_bf16 = clibd_layernorm_bwd with the residual gradient read and written as bf16: fed the bf16
     image of the fp32 call's residual it must reproduce that call's dx bit for bit (same arithmetic, fp32 inside), as an
     un-dropped residual copy and — under dropout — a masked copy for the dense branch."""
     g = torch.Generator().manual_seed(M + H)
@@ -1204,7 +1204,7 @@ def test_layernorm_bwd_bf16_residual_stream(ops, dev, M, H, f32dy, drop):
 
 @pytest.mark.parametrize("M,H,f32dy,drop", [(777, 768, False, True), (5000, 768, True, False), (64, 512, False, False)])
 def test_layernorm_bwd_any_bf16_stream_with_param_grads(ops, dev, M, H, f32dy, drop):
-    """clibd_layernorm_bwd_any (round 4: full fine-tune on the bf16 residual-gradient stream): the bf16-stream backward with
+    """clibd_layernorm_bwd, every optional operand at once (round 4: full fine-tune on the bf16 residual-gradient stream): the bf16-stream backward with
     d(gamma), d(beta) accumulated in the same pass and, for the bottom layer, an fp32 dx beside the bf16 copies — every output equal
     to what the separate entry points give (res16 for dx, pg for the parameter gradients), bit for bit."""
     g = torch.Generator().manual_seed(M * 3 + H)

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void ln_t(const float* __restrict__ x, const f
     }
 }
 
-typedef int (*attn_fwd_fn)(const void*, int, int, int, const int*, void*, int, int, void*);
+typedef int (*attn_fwd_fn)(const void*, int, int, int, const int*, void*, int, int, uint32_t, int, float, float, float*, void*, void*);
 
 static float frand(unsigned& s) { s = s * 1664525u + 1013904223u; return ((s >> 8) & 0xffff) / 65536.0f - 0.5f; }
 
@@ -181,7 +181,7 @@ int main(int argc, char** argv) {
         // ---- canary
         CHECK(hipMemset(derr, 0, 8)); CHECK(hipMemset(dbad, 0, 16));
         for (int r = 0; r < rounds; ++r) {
-            if (mode) for (int k = 0; k < per_round; ++k) { if (attn(qkv, B, S, NH, nullptr, aout, S, S, (void*)s2) != 0) { printf("attention launch failed\n"); return 1; } }
+            if (mode) for (int k = 0; k < per_round; ++k) { if (attn(qkv, B, S, NH, nullptr, aout, S, S, 0u, 0, 1.0f, 0.f, nullptr, nullptr, (void*)s2) != 0) { printf("attention launch failed\n"); return 1; } }
             hipLaunchKernelGGL(canary, dim3(2048), dim3(256), LDS_WORDS * 4, s1, 24, derr, dbad);
         }
         CHECK(hipDeviceSynchronize());
@@ -195,7 +195,7 @@ int main(int argc, char** argv) {
             int total_bad = 0, launches_bad = 0;
             for (int r = 0; r < rounds; ++r) {
                 CHECK(hipMemsetAsync(dt, 0, (size_t)M * 8 * 4, s1));
-                if (mode) for (int k = 0; k < per_round; ++k) attn(qkv, B, S, NH, nullptr, aout, S, S, (void*)s2);
+                if (mode) for (int k = 0; k < per_round; ++k) attn(qkv, B, S, NH, nullptr, aout, S, S, 0u, 0, 1.0f, 0.f, nullptr, nullptr, (void*)s2);
                 if (bperm) hipLaunchKernelGGL(ln_t<true>, dim3(2048), dim3(256), LDS_WORDS * 4, s1, dx, dA, M, dt);
                 else hipLaunchKernelGGL(ln_t<false>, dim3(2048), dim3(256), LDS_WORDS * 4, s1, dx, dA, M, dt);
                 CHECK(hipDeviceSynchronize());
