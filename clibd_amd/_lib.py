@@ -50,9 +50,8 @@ SIGNATURES = {
     "clibd_last_error": (C.c_char_p, []),
     "clibd_abi_version": (c_int, []),
     "clibd_build_hash": (C.c_char_p, []),
-    "clibd_gemm_bf16_nt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, C.POINTER(GemmEpilogue), c_void_p]),
     "clibd_gemm_tail_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "clibd_gemm_bf16_nt_ws": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, C.POINTER(GemmEpilogue), c_void_p, c_size_t, c_void_p]),
+    "clibd_gemm_bf16_nt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, C.POINTER(GemmEpilogue), c_void_p, c_size_t, c_void_p]),
     "clibd_gemm_bf16_nt_khole": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(GemmEpilogue), c_void_p]),
     "clibd_gemm_fp8_nt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, C.POINTER(GemmEpilogue), c_void_p]),
     "clibd_quantize_rows_fp8": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
@@ -60,9 +59,8 @@ SIGNATURES = {
     "clibd_quantize_rows_fp8_bf16": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "clibd_transpose_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "clibd_transpose_fp8_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
-    "clibd_transpose_colsum_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "clibd_transpose_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "clibd_transpose_colsum_bf16_ws": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_transpose_colsum_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "clibd_cast_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "clibd_cast_transpose_f32_to_bf16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "clibd_layernorm_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -90,7 +88,8 @@ SIGNATURES = {
     "clibd_softmax_mean_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "clibd_token_mean_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "clibd_token_mean_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "clibd_colsum_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "clibd_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_colsum_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "clibd_gather_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "clibd_scatter_rows_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "clibd_l2norm_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -113,36 +112,28 @@ SIGNATURES = {
     "clibd_threshold_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, C.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "clibd_image_transform_workspace_bytes": (c_size_t, [c_int]),
     "clibd_image_transform_u8": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "clibd_layernorm_param_grads": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
+    # the reductions: (workspace, workspace_bytes) before the stream; (None, 0) selects the atomic form
+    "clibd_layernorm_param_grads_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_layernorm_param_grads": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, C.c_uint32, c_int, c_float,
+                                            c_void_p, c_size_t, c_void_p]),
     "clibd_gemm_splitk_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "clibd_gemm_bf16_tn_splitk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "clibd_gemm_fp8b_tn_splitk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                          c_size_t, c_void_p]),
-    "clibd_gemm_fp8b_tn_splitk_ordered": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
-                                                  c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "clibd_gemm_tn_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_gemm_bf16_tn_splitk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                          c_void_p, c_size_t, c_void_p]),
+    "clibd_gemm_fp8b_tn_splitk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                                          c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "clibd_gemm_bf16_nt_splitk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "clibd_dropout_apply_f32": (c_int, [c_void_p, c_size_t, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
-    "clibd_batch_sum_f32": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p]),
-    "clibd_bert_embed_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "clibd_slice_rows_cast_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    # deterministic mode (partials workspaces + fixed-order sums)
-    "clibd_layernorm_param_grads_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "clibd_layernorm_param_grads_ordered": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, C.c_uint32, c_int, c_float,
-                                                    c_void_p, c_size_t, c_void_p]),
     "clibd_batch_sum_workspace_bytes": (c_size_t, [c_int, c_size_t]),
-    "clibd_batch_sum_f32_ordered": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_batch_sum_f32": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
     "clibd_bert_embed_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "clibd_bert_embed_bwd_ordered": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "clibd_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "clibd_colsum_bf16_ordered": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "clibd_gemm_tn_colsum_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "clibd_gemm_bf16_tn_splitk_ordered": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
-                                                  c_void_p, c_size_t, c_void_p]),
+    "clibd_bert_embed_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_slice_rows_cast_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "clibd_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
 }
 
 _lib = None
-ABI_VERSION = 6   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
+ABI_VERSION = 7   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
 
 class ClibdHipError(RuntimeError):

@@ -591,29 +591,22 @@ extern "C" int clibd_token_mean_bwd(const float* dout, int B, int S, int H, floa
     return check_launch("token_mean_bwd");
 }
 
-extern "C" int clibd_colsum_bf16(const void* x, int ld, int M, int N, float* out, void* stream) {
-    if (!x || !out || M <= 0 || N <= 0 || ld < N) return set_error(CLIBD_EINVAL, "colsum: bad args");
-    dim3 grid((N + 63) / 64, (M + 255) / 256);
-    hipLaunchKernelGGL(colsum_bf16_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ld, M, N, out, (float*)nullptr);
-    return check_launch("colsum_bf16");
-}
-
-// deterministic mode: at most COLSUM_ORDERED_ROWS partial rows (chunk-strided), then ordered_colsum_kernel
+// NULL workspace: one block row per 256 rows and float atomics; with a workspace (deterministic mode) at most COLSUM_ORDERED_ROWS
+// partial rows (chunk-strided), then ordered_colsum_kernel
 constexpr int COLSUM_ORDERED_ROWS = 256;
 extern "C" size_t clibd_colsum_workspace_bytes(int M, int N) {
     if (M <= 0 || N <= 0) return 0;
     return (size_t)min((M + 255) / 256, COLSUM_ORDERED_ROWS) * (size_t)N * sizeof(float);
 }
 
-extern "C" int clibd_colsum_bf16_ordered(const void* x, int ld, int M, int N, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !out || !workspace || M <= 0 || N <= 0 || ld < N) return set_error(CLIBD_EINVAL, "colsum_ordered: bad args");
-    if (!aligned16(workspace) || workspace_bytes < clibd_colsum_workspace_bytes(M, N))
-        return set_error(CLIBD_EINVAL, "colsum_ordered: workspace too small or misaligned (clibd_colsum_workspace_bytes)");
-    const int rows = min((M + 255) / 256, COLSUM_ORDERED_ROWS);
+extern "C" int clibd_colsum_bf16(const void* x, int ld, int M, int N, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !out || M <= 0 || N <= 0 || ld < N) return set_error(CLIBD_EINVAL, "colsum: bad args");
+    if (int e = check_workspace("colsum", "workspace", workspace, workspace_bytes, clibd_colsum_workspace_bytes(M, N), "clibd_colsum_workspace_bytes")) return e;
+    const int rows = workspace ? min((M + 255) / 256, COLSUM_ORDERED_ROWS) : (M + 255) / 256;
     hipLaunchKernelGGL(colsum_bf16_kernel, dim3((N + 63) / 64, rows), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, ld, M, N, out,
                        (float*)workspace);
-    if (int e = check_launch("colsum_bf16_ordered")) return e;
-    return ordered_colsum_launch((const float*)workspace, rows, N, out, N, nullptr, (hipStream_t)stream);
+    if (int e = check_launch("colsum_bf16")) return e;
+    return workspace ? ordered_colsum_launch((const float*)workspace, rows, N, out, N, nullptr, (hipStream_t)stream) : CLIBD_OK;
 }
 
 extern "C" int clibd_gather_rows(const float* x, int B, int S, int H, float* out, void* stream) {

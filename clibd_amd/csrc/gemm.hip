@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void transpose_colsum_bf16_kernel(const unsign
 }
 
 // colsum[c] += sum_b partials[b, c] in the fixed order b = 0, 1, ... (four interleaved chains, combined in a fixed order): the bias
-// gradient of the workspace form of the transpose (clibd_transpose_colsum_bf16_ws) repeats bit for bit from run to run.
+// gradient of the workspace form of the transpose (clibd_transpose_colsum_bf16 with a workspace) repeats bit for bit from run to run.
 __global__ __launch_bounds__(256) void colsum_partials_kernel(const float* __restrict__ partials, int nblk, int C, float* __restrict__ colsum) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(256) void cast_transpose_f32_bf16_kernel(const floa
 using namespace clibd;
 
 static int gemm_impl(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int hole_k0, int hole_len,
-                     const clibd_gemm_epilogue* ep, void* stream, void* tail_ws = nullptr, size_t tail_ws_bytes = 0) {
+                     const clibd_gemm_epilogue* ep, void* tail_ws, size_t tail_ws_bytes, void* stream) {
     if (!A || !W || !ep) return set_error(CLIBD_EINVAL, "gemm: null pointer");
     if (hole_len < 0 || hole_k0 < 0 || hole_k0 % BK || hole_len % BK || hole_k0 + hole_len > K || (hole_len > 0 && hole_len >= K))
         return set_error(CLIBD_EINVAL, "gemm: bad K hole (multiples of 64 inside [0, K))");
@@ -396,13 +396,12 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, int M, int 
     p.splits = 1; p.nk_split = 0; p.split_stride = 0;
     p.hole_kt = hole_len > 0 ? hole_k0 / BK : 0x7fffffff;
     p.hole_nkt = hole_len / BK;
-    if (tail_ws != nullptr) {   // stream-K tail workspace: [256 flag words | fp32 partial tiles]; ignored when the shape has no use for it
-        const size_t need = gemm256_tail_workspace_bytes(M, N, K);
-        if (need > 0) {
-            if (tail_ws_bytes < need || !aligned16(tail_ws)) return set_error(CLIBD_EINVAL, "gemm: tail workspace too small or misaligned (clibd_gemm_tail_workspace_bytes)");
-            p.sk_flags = (unsigned*)tail_ws;
-            p.sk_ws = (float*)((char*)tail_ws + 1024);
-        }
+    // stream-K tail workspace: [256 flag words | fp32 partial tiles]; a shape that has no use for it (need == 0) ignores it
+    const size_t tail_need = gemm256_tail_workspace_bytes(M, N, K);
+    if (int e = check_workspace("gemm", "tail workspace", tail_ws, tail_ws_bytes, tail_need, "clibd_gemm_tail_workspace_bytes")) return e;
+    if (tail_ws != nullptr && tail_need > 0) {
+        p.sk_flags = (unsigned*)tail_ws;
+        p.sk_ws = (float*)((char*)tail_ws + 1024);
     }
     // kernel choice (CLIBD_GEMM_KERNEL=1 forces the 128x128 kernel: tuning aid).  A third shape — 256x128x32 tiles, 3-stage
     // ring, two workgroups per CU so epilogues overlap across workgroups — was built and measured: 800 TF at K=768 and
@@ -432,21 +431,16 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, int M, int 
     return check_launch("gemm_bf16_nt");
 }
 
-extern "C" int clibd_gemm_bf16_nt(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
-                                  const clibd_gemm_epilogue* ep, void* stream) {
-    return gemm_impl(A, lda, W, ldw, M, N, K, 0, 0, ep, stream);
-}
-
 extern "C" size_t clibd_gemm_tail_workspace_bytes(int M, int N, int K) { return gemm256_tail_workspace_bytes(M, N, K); }
 
-extern "C" int clibd_gemm_bf16_nt_ws(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
-                                     const clibd_gemm_epilogue* ep, void* workspace, size_t workspace_bytes, void* stream) {
-    return gemm_impl(A, lda, W, ldw, M, N, K, 0, 0, ep, stream, workspace, workspace_bytes);
+extern "C" int clibd_gemm_bf16_nt(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
+                                  const clibd_gemm_epilogue* ep, void* workspace, size_t workspace_bytes, void* stream) {
+    return gemm_impl(A, lda, W, ldw, M, N, K, 0, 0, ep, workspace, workspace_bytes, stream);
 }
 
 extern "C" int clibd_gemm_bf16_nt_khole(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int hole_k0, int hole_len,
                                         const clibd_gemm_epilogue* ep, void* stream) {
-    return gemm_impl(A, lda, W, ldw, M, N, K, hole_k0, hole_len, ep, stream);
+    return gemm_impl(A, lda, W, ldw, M, N, K, hole_k0, hole_len, ep, nullptr, 0, stream);
 }
 
 extern "C" int clibd_gemm_fp8_nt(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* col_scale,
@@ -523,6 +517,14 @@ extern "C" size_t clibd_gemm_splitk_workspace_bytes(int M, int N) {
     return (size_t)256 * (size_t)M * (size_t)N * sizeof(float) / (size_t)(((M + 255) / 256) * ((N + 255) / 256));  // <= 256 work items per round
 }
 
+static int reduce_splits_launch(const float* partials, int splits, size_t n_elems, float* out, int accumulate, hipStream_t stream) {
+    const size_t n4 = n_elems / 4;
+    size_t blocks = (n4 + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, partials, splits, n4, out, accumulate);
+    return check_launch("reduce_splits");
+}
+
 extern "C" int clibd_gemm_bf16_nt_splitk(const void* A, int lda, const void* W, int ldw, int M, int N, int K, float* out_f32, int ld_out,
                                          int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
     if (!A || !W || !out_f32 || !workspace) return set_error(CLIBD_EINVAL, "gemm_splitk: null pointer");
@@ -535,107 +537,64 @@ extern "C" int clibd_gemm_bf16_nt_splitk(const void* A, int lda, const void* W, 
     const int splits = gemm256_splitk_launch(p, (float*)workspace, workspace_bytes / sizeof(float), (hipStream_t)stream);
     if (splits <= 0) return set_error(CLIBD_EINVAL, "gemm_splitk: shape not supported (need N % 256 == 0, K % 128 == 0, K >= 512, workspace)");
     if (int e = check_launch("gemm256_splitk")) return e;
-    const size_t n4 = (size_t)M * N / 4;
-    size_t blocks = (n4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, splits, n4,
-                       out_f32, accumulate);
-    return check_launch("reduce_splits");
+    return reduce_splits_launch((const float*)workspace, splits, (size_t)M * N, out_f32, accumulate, (hipStream_t)stream);
 }
 
-extern "C" int clibd_gemm_bf16_tn_splitk(const void* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* out_f32, int ld_out,
-                                         int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!A || !B || !out_f32 || !workspace) return set_error(CLIBD_EINVAL, "gemm_tn_splitk: null pointer");
-    if (M <= 0 || Na <= 0 || Nb <= 0 || lda < Na || ldb < Nb || ld_out != Nb) return set_error(CLIBD_EINVAL, "gemm_tn_splitk: bad shape (out must be dense [Na,Nb])");
-    if ((lda & 7) || (ldb & 7) || !aligned16(A) || !aligned16(B) || !aligned16(out_f32) || !aligned16(workspace))
-        return set_error(CLIBD_EINVAL, "gemm_tn_splitk: alignment");
-    const int splits = gemm256_tn_splitk_launch((const unsigned short*)A, lda, (const unsigned short*)B, ldb, M, Na, Nb, (float*)workspace,
-                                                workspace_bytes / sizeof(float), colsum_a, (hipStream_t)stream);
-    if (splits <= 0) return set_error(CLIBD_EINVAL, "gemm_tn_splitk: shape not supported (need M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, workspace)");
-    if (int e = check_launch("gemm256_tn")) return e;
-    const size_t n4 = (size_t)Na * Nb / 4;
-    size_t blocks = (n4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, splits, n4,
-                       out_f32, accumulate);
-    return check_launch("reduce_splits");
-}
-
-// deterministic mode: the TN split-K weight gradient whose bias gradient (colsum_a) is stored as one partial per M-slice (at most
-// M / 256 slices: plan_k_slices keeps every slice >= 4 K-tiles) and summed in slice order, after the slices' reduce_splits_kernel
+// the bias gradient (colsum_a) of the TN weight gradient in deterministic mode: one partial per M-slice (at most M / 256 slices:
+// plan_k_slices keeps every slice >= 4 K-tiles), summed in slice order after the slices' reduce_splits_kernel
 extern "C" size_t clibd_gemm_tn_colsum_workspace_bytes(int M, int Na) {
     if (M <= 0 || Na <= 0) return 0;
     const int slots = M / 256 > 1 ? M / 256 : 1;
     return (size_t)slots * (size_t)Na * sizeof(float);
 }
 
-extern "C" int clibd_gemm_bf16_tn_splitk_ordered(const void* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* out_f32, int ld_out,
-                                                 int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
-                                                 size_t colsum_workspace_bytes, void* stream) {
-    if (!A || !B || !out_f32 || !workspace || !colsum_a || !colsum_workspace) return set_error(CLIBD_EINVAL, "gemm_tn_splitk_ordered: null pointer");
-    if (M <= 0 || Na <= 0 || Nb <= 0 || lda < Na || ldb < Nb || ld_out != Nb) return set_error(CLIBD_EINVAL, "gemm_tn_splitk_ordered: bad shape (out must be dense [Na,Nb])");
-    if ((lda & 7) || (ldb & 7) || !aligned16(A) || !aligned16(B) || !aligned16(out_f32) || !aligned16(workspace) || !aligned16(colsum_workspace))
-        return set_error(CLIBD_EINVAL, "gemm_tn_splitk_ordered: alignment");
-    if (colsum_workspace_bytes < clibd_gemm_tn_colsum_workspace_bytes(M, Na))
-        return set_error(CLIBD_EINVAL, "gemm_tn_splitk_ordered: colsum workspace too small (clibd_gemm_tn_colsum_workspace_bytes)");
-    const int splits = gemm256_tn_splitk_launch((const unsigned short*)A, lda, (const unsigned short*)B, ldb, M, Na, Nb, (float*)workspace,
-                                                workspace_bytes / sizeof(float), colsum_a, (hipStream_t)stream, (float*)colsum_workspace);
-    if (splits <= 0) return set_error(CLIBD_EINVAL, "gemm_tn_splitk_ordered: shape not supported (need M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, workspace)");
+// Both TN entry points.  b_scale == 0: B is bf16; b_scale > 0: B is the e4m3 image the forward GEMM consumed (full fine-tune under the fp8
+// forward), dequantised by b_scale in the kernel's fp32 epilogue.  colsum_workspace: NULL = colsum_a (if any) by float atomics.
+static int tn_splitk_impl(const void* A, int lda, const void* B, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32, int ld_out,
+                          int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
+                          size_t colsum_workspace_bytes, void* stream) {
+    const bool b8 = b_scale > 0.f;
+    const char* op = b8 ? "gemm_fp8b_tn_splitk" : "gemm_tn_splitk";
+    auto fail = [op](const char* what) {
+        char msg[kErrBufLen];
+        snprintf(msg, sizeof msg, "%s: %s", op, what);
+        return set_error(CLIBD_EINVAL, msg);
+    };
+    if (!A || !B || !out_f32 || !workspace) return fail("null pointer");
+    if (M <= 0 || Na <= 0 || Nb <= 0 || lda < Na || ldb < Nb || ld_out != Nb) return fail("bad shape (out must be dense [Na,Nb])");
+    if ((lda & 7) || (ldb & 7) || !aligned16(A) || ((uintptr_t)B & (b8 ? 7 : 15)) || !aligned16(out_f32) || !aligned16(workspace)) return fail("alignment");
+    if (int e = check_workspace(op, "colsum workspace", colsum_workspace, colsum_workspace_bytes, clibd_gemm_tn_colsum_workspace_bytes(M, Na),
+                                "clibd_gemm_tn_colsum_workspace_bytes"))
+        return e;
+    if (colsum_workspace && !colsum_a) return fail("a colsum workspace needs colsum_a");
+    const int splits = gemm256_tn_splitk_launch((const unsigned short*)A, lda, B, ldb, M, Na, Nb, (float*)workspace, workspace_bytes / sizeof(float),
+                                                colsum_a, (hipStream_t)stream, (float*)colsum_workspace, b_scale);
+    if (splits <= 0) return fail("shape not supported (need M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, workspace)");
     if (int e = check_launch("gemm256_tn")) return e;
-    const size_t n4 = (size_t)Na * Nb / 4;
-    size_t blocks = (n4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, splits, n4,
-                       out_f32, accumulate);
-    if (int e = check_launch("reduce_splits")) return e;
+    if (int e = reduce_splits_launch((const float*)workspace, splits, (size_t)Na * Nb, out_f32, accumulate, (hipStream_t)stream)) return e;
+    if (!colsum_workspace) return CLIBD_OK;
     return ordered_colsum_launch((const float*)colsum_workspace, splits, Na, colsum_a, Na, nullptr, (hipStream_t)stream);
 }
 
-// full fine-tune under the fp8 forward: the TN weight gradient whose B operand (the layer input X) is the e4m3 image the forward GEMM
-// consumed, dequantised by b_scale in the kernel's fp32 epilogue; same split plan, workspaces and column-sum forms as the bf16 entry points
-static int tn_fp8b_impl(const void* A, int lda, const void* B8, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32, int ld_out,
-                        int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
-                        size_t colsum_workspace_bytes, bool ordered, void* stream) {
-    const char* what = ordered ? "gemm_fp8b_tn_splitk_ordered" : "gemm_fp8b_tn_splitk";
-    if (!A || !B8 || !out_f32 || !workspace || (ordered && (!colsum_a || !colsum_workspace))) return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk: null pointer");
-    if (M <= 0 || Na <= 0 || Nb <= 0 || lda < Na || ldb < Nb || ld_out != Nb || !(b_scale > 0.f) || !std::isfinite(b_scale))
-        return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk: bad shape (out must be dense [Na,Nb]) or b_scale (finite, > 0)");
-    if ((lda & 7) || (ldb & 7) || !aligned16(A) || ((uintptr_t)B8 & 7) || !aligned16(out_f32) || !aligned16(workspace) ||
-        (ordered && !aligned16(colsum_workspace)))
-        return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk: alignment");
-    if (ordered && colsum_workspace_bytes < clibd_gemm_tn_colsum_workspace_bytes(M, Na))
-        return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk_ordered: colsum workspace too small (clibd_gemm_tn_colsum_workspace_bytes)");
-    const int splits = gemm256_tn_fp8b_splitk_launch((const unsigned short*)A, lda, (const unsigned char*)B8, ldb, b_scale, M, Na, Nb, (float*)workspace,
-                                                     workspace_bytes / sizeof(float), colsum_a, (hipStream_t)stream,
-                                                     ordered ? (float*)colsum_workspace : nullptr);
-    if (splits <= 0) return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk: shape not supported (need M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, workspace)");
-    if (int e = check_launch(what)) return e;
-    const size_t n4 = (size_t)Na * Nb / 4;
-    size_t blocks = (n4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, splits, n4,
-                       out_f32, accumulate);
-    if (int e = check_launch("reduce_splits")) return e;
-    if (!ordered) return CLIBD_OK;
-    return ordered_colsum_launch((const float*)colsum_workspace, splits, Na, colsum_a, Na, nullptr, (hipStream_t)stream);
+extern "C" int clibd_gemm_bf16_tn_splitk(const void* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* out_f32, int ld_out,
+                                         int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
+                                         size_t colsum_workspace_bytes, void* stream) {
+    return tn_splitk_impl(A, lda, B, ldb, 0.f, M, Na, Nb, out_f32, ld_out, accumulate, colsum_a, workspace, workspace_bytes, colsum_workspace,
+                          colsum_workspace_bytes, stream);
 }
 
 extern "C" int clibd_gemm_fp8b_tn_splitk(const void* A, int lda, const void* B8, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32,
-                                         int ld_out, int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* stream) {
-    return tn_fp8b_impl(A, lda, B8, ldb, b_scale, M, Na, Nb, out_f32, ld_out, accumulate, colsum_a, workspace, workspace_bytes, nullptr, 0, false, stream);
-}
-
-extern "C" int clibd_gemm_fp8b_tn_splitk_ordered(const void* A, int lda, const void* B8, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32,
-                                                 int ld_out, int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes,
-                                                 void* colsum_workspace, size_t colsum_workspace_bytes, void* stream) {
-    return tn_fp8b_impl(A, lda, B8, ldb, b_scale, M, Na, Nb, out_f32, ld_out, accumulate, colsum_a, workspace, workspace_bytes, colsum_workspace,
-                        colsum_workspace_bytes, true, stream);
+                                         int ld_out, int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes,
+                                         void* colsum_workspace, size_t colsum_workspace_bytes, void* stream) {
+    if (!(b_scale > 0.f) || !std::isfinite(b_scale)) return set_error(CLIBD_EINVAL, "gemm_fp8b_tn_splitk: b_scale must be finite and > 0");
+    return tn_splitk_impl(A, lda, B8, ldb, b_scale, M, Na, Nb, out_f32, ld_out, accumulate, colsum_a, workspace, workspace_bytes, colsum_workspace,
+                          colsum_workspace_bytes, stream);
 }
 
 static inline int transpose_row_tile(int ld_out) { return ld_out >= 1024 ? 256 : 64; }
 
-static int transpose_impl(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, void* stream,
-                          float* partials = nullptr, size_t partials_bytes = 0) {
+// partials: NULL, or the workspace of clibd_transpose_colsum_bf16 (validated there)
+static int transpose_impl(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, float* partials, void* stream) {
     if (!in || !out || R <= 0 || C <= 0 || ld_in < C || ld_out < R) return set_error(CLIBD_EINVAL, "transpose: bad args");
     dim3 grid((C + 63) / 64, (ld_out + 63) / 64);
     if (grid.y > 65535u) return set_error(CLIBD_EINVAL, "transpose: too many rows for one launch");
@@ -643,8 +602,6 @@ static int transpose_impl(const void* in, int ld_in, int R, int C, void* out, in
     if (fast) {
         const int tile_rows = transpose_row_tile(ld_out);
         const int nblk = (ld_out + tile_rows - 1) / tile_rows;
-        if (partials != nullptr && (partials_bytes < (size_t)nblk * C * sizeof(float) || ((uintptr_t)partials & 3)))
-            return set_error(CLIBD_EINVAL, "transpose_colsum: workspace too small (clibd_transpose_colsum_workspace_bytes)");
         if (tile_rows == 256) {   // long row dimension (activations): 256-row tiles
             dim3 grid4((C + 63) / 64, nblk);
             hipLaunchKernelGGL(transpose_colsum_bf16_kernel<4>, grid4, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)in, ld_in, R, C,
@@ -667,7 +624,7 @@ static int transpose_impl(const void* in, int ld_in, int R, int C, void* out, in
 }
 
 extern "C" int clibd_transpose_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, void* stream) {
-    return transpose_impl(in, ld_in, R, C, out, ld_out, nullptr, stream);
+    return transpose_impl(in, ld_in, R, C, out, ld_out, nullptr, nullptr, stream);
 }
 
 extern "C" int clibd_transpose_fp8_bf16(const void* in, int ld_in, int R, int C, float scale, void* out, int ld_out, void* stream) {
@@ -679,21 +636,19 @@ extern "C" int clibd_transpose_fp8_bf16(const void* in, int ld_in, int R, int C,
     return check_launch("transpose_fp8_bf16");
 }
 
-extern "C" int clibd_transpose_colsum_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, void* stream) {
-    if (!colsum) return set_error(CLIBD_EINVAL, "transpose_colsum: null colsum");
-    return transpose_impl(in, ld_in, R, C, out, ld_out, colsum, stream);
-}
-
 extern "C" size_t clibd_transpose_colsum_workspace_bytes(int ld_out, int C) {
     if (ld_out <= 0 || C <= 0) return 0;
     const int tile_rows = transpose_row_tile(ld_out);
     return (size_t)((ld_out + tile_rows - 1) / tile_rows) * (size_t)C * sizeof(float);
 }
 
-extern "C" int clibd_transpose_colsum_bf16_ws(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, void* workspace,
-                                              size_t workspace_bytes, void* stream) {
-    if (!colsum || !workspace) return set_error(CLIBD_EINVAL, "transpose_colsum_ws: null colsum / workspace");
-    return transpose_impl(in, ld_in, R, C, out, ld_out, colsum, stream, (float*)workspace, workspace_bytes);
+extern "C" int clibd_transpose_colsum_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    if (!colsum) return set_error(CLIBD_EINVAL, "transpose_colsum: null colsum");
+    if (int e = check_workspace("transpose_colsum", "workspace", workspace, workspace_bytes, clibd_transpose_colsum_workspace_bytes(ld_out, C),
+                                "clibd_transpose_colsum_workspace_bytes"))
+        return e;
+    return transpose_impl(in, ld_in, R, C, out, ld_out, colsum, (float*)workspace, stream);
 }
 
 extern "C" int clibd_cast_f32_to_bf16(const float* in, void* out, size_t n, void* stream) {

@@ -992,7 +992,7 @@ bool gemm256_try_launch(const GemmParams& p, hipStream_t stream) {
     if (kind < 0) return false;                                   // an inconsistent fold epilogue (gemm_impl reports it)
     const void* fn = kernel_ptr(kind, lora, p.ep.bias != nullptr, diag);
     if (fn == nullptr) return false;
-    // Stream-K tail (round 6): with a workspace from the caller (clibd_gemm_bf16_nt_ws), a launch whose last round is at most half full and whose
+    // Stream-K tail (round 6): with a workspace from the caller (clibd_gemm_bf16_nt), a launch whose last round is at most half full and whose
     // contraction is long cuts that round's tiles into K-slices over the idle CUs
     q.sk_parts = 0;
     if (p.sk_ws != nullptr && p.sk_flags != nullptr && !diag) {

@@ -330,9 +330,9 @@ __global__ __launch_bounds__(TN_THREADS) void gemm256_tn_kernel(TnParams p, int 
     }
 }
 
-// Returns the number of M-slices used (>= 1) or 0 when the shape is not one this kernel takes.  b_scale > 0: B is e4m3 (B8).
-static int tn_splitk_launch(const unsigned short* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* partials,
-                            size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials, float b_scale) {
+// Returns the number of M-slices used (>= 1) or 0 when the shape is not one this kernel takes.  b_scale > 0: B is e4m3 (B8); 0: bf16.
+int gemm256_tn_splitk_launch(const unsigned short* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* partials,
+                             size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials, float b_scale) {
     if (M <= 0 || M % 128 != 0 || Na % 256 != 0 || Nb % 256 != 0 || Na <= 0 || Nb <= 0) return 0;
     const int nk = M / 64;
     if (nk < 4) return 0;
@@ -372,17 +372,6 @@ static int tn_splitk_launch(const unsigned short* A, int lda, const void* B, int
                                        : (b8 ? (const void*)gemm256_tn_kernel<false, true> : (const void*)gemm256_tn_kernel<false, false>);
     if (hipLaunchKernel(fn, dim3((unsigned)grid), dim3(TN_THREADS), args, TN_LDS, stream) != hipSuccess) return 0;
     return splits;
-}
-
-int gemm256_tn_splitk_launch(const unsigned short* A, int lda, const unsigned short* B, int ldb, int M, int Na, int Nb, float* partials,
-                             size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials) {
-    return tn_splitk_launch(A, lda, B, ldb, M, Na, Nb, partials, partials_elems, colsum, stream, colsum_partials, 0.f);
-}
-
-int gemm256_tn_fp8b_splitk_launch(const unsigned short* A, int lda, const unsigned char* B8, int ldb, float b_scale, int M, int Na, int Nb,
-                                  float* partials, size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials) {
-    if (!(b_scale > 0.f)) return 0;
-    return tn_splitk_launch(A, lda, B8, ldb, M, Na, Nb, partials, partials_elems, colsum, stream, colsum_partials, b_scale);
 }
 
 }  // namespace clibd

@@ -30,7 +30,7 @@ struct GemmParams {
     // 8-bit dgrad under full fine-tune (round 6): the MUL_AUX forms also write the DE-SCALED value as bf16 (the weight gradient's operand)
     unsigned short* dual_bf16;
     int ld_dual;
-    // Stream-K tail (round 6, gemm256 SK instantiations; clibd_gemm_bf16_nt_ws): the tiles of the LAST, partial round of the persistent grid are cut
+    // Stream-K tail (round 6, gemm256 SK instantiations; clibd_gemm_bf16_nt with a workspace): the tiles of the LAST, partial round of the persistent grid are cut
     // into sk_parts K-slices, one work item each.  Work items sk_first .. sk_first + sk_tail * sk_parts - 1 are those slices, non-owners first
     // (slot j % sk_tail, part 1 + j / sk_tail), owners (part 0) last: a workgroup's id is also its dispatch order, so an owner's partners are
     // always dispatched before it.  Part q covers K-tiles [q * sk_nk_part, min((q + 1) * sk_nk_part, K / 64)); parts >= 1 store their fp32 partial
@@ -575,11 +575,9 @@ bool gemm256_fp8_dgrad_launch(const GemmParams& p, hipStream_t stream);
 int gemm256_splitk_launch(const GemmParams& p, float* partials, size_t partials_elems, hipStream_t stream);
 
 // rows-contracting ("TN") split-M GEMM, gemm256_tn.hip: partials[s] (fp32 [Na, Nb]) = A[slice s, :Na]^T · B[slice s, :Nb];
-// returns the number of slices (0: shape not taken)
-int gemm256_tn_splitk_launch(const unsigned short* A, int lda, const unsigned short* B, int ldb, int M, int Na, int Nb, float* partials,
-                             size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials = nullptr);
-// the same with B as e4m3 bytes (ldb in bytes) and the tile multiplied by b_scale (> 0) before it is stored
-int gemm256_tn_fp8b_splitk_launch(const unsigned short* A, int lda, const unsigned char* B8, int ldb, float b_scale, int M, int Na, int Nb,
-                                  float* partials, size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials = nullptr);
+// returns the number of slices (0: shape not taken).  b_scale > 0: B is e4m3 bytes (ldb in bytes) and the tile is multiplied by b_scale
+// before it is stored; 0: B is bf16.  colsum_partials: NULL = colsum (if any) by float atomics, else one partial per slice.
+int gemm256_tn_splitk_launch(const unsigned short* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* partials,
+                             size_t partials_elems, float* colsum, hipStream_t stream, float* colsum_partials, float b_scale);
 
 }  // namespace clibd

@@ -17,6 +17,16 @@ inline int set_error(int code, const char* msg) {
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// The workspace rule of the reduction entry points (include/clibd_hip.h, "deterministic mode"): NULL with size 0 selects the atomic / plain
+// form; NULL with a size, a misaligned or a short workspace is CLIBD_EINVAL, and the message names the size query.  `need` = that query's answer.
+inline int check_workspace(const char* op, const char* name, const void* ws, size_t bytes, size_t need, const char* query) {
+    if (ws == nullptr ? bytes == 0 : (aligned16(ws) && bytes >= need)) return 0;
+    char msg[kErrBufLen];
+    if (ws == nullptr) snprintf(msg, sizeof msg, "%s: %s size without a %s", op, name, name);
+    else snprintf(msg, sizeof msg, "%s: %s too small or misaligned (%s)", op, name, query);
+    return set_error(-1, msg);
+}
+
 // Launch-time errors only (no synchronisation): configuration errors surface here, device faults do not.
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

@@ -230,7 +230,7 @@ extern "C" int clibd_softce_rows_fwd(const float* x, const float* y, const int64
     ep.out_f32 = w.S;  // raw similarities <x_i, y_j>
     ep.ld_out_f32 = N16;
     ep.split_k = 1;
-    if (int e = clibd_gemm_bf16_nt(w.x3, 3 * D, w.y3, 3 * D, Nx, N16, 3 * D, &ep, stream)) return e;
+    if (int e = clibd_gemm_bf16_nt(w.x3, 3 * D, w.y3, 3 * D, Nx, N16, 3 * D, &ep, nullptr, 0, stream)) return e;
     hipLaunchKernelGGL(softce_rows_fwd_kernel, dim3((Nx + 3) / 4), dim3(256), 0, st, w.S, N16, Nx, N, labels, row0, scale,
                        w.lse, w.tsum, w.rows);
     if (int e = check_launch("softce_rows_fwd")) return e;
@@ -265,9 +265,9 @@ extern "C" int clibd_softce_rows_bwd(const int64_t* labels, int Nx, int N, int D
     ep.split_k = 1;
     // dx[i,:] += sum_j G[i,j] y[j,:]      (accumulate in place through the residual path)
     ep.out_f32 = dx; ep.ld_out_f32 = D; ep.residual_f32 = dx; ep.ld_res = D;
-    if (int e = clibd_gemm_bf16_nt(w.G, 3 * Np, w.yT, 3 * Np, Nx, D, 3 * Np, &ep, stream)) return e;
+    if (int e = clibd_gemm_bf16_nt(w.G, 3 * Np, w.yT, 3 * Np, Nx, D, 3 * Np, &ep, nullptr, 0, stream)) return e;
     // dy[j,:] += sum_i G[i,j] x[i,:]
     ep.out_f32 = dy; ep.residual_f32 = dy;
-    if (int e = clibd_gemm_bf16_nt(w.GT, 3 * Nxp, w.xT, 3 * Nxp, N, D, 3 * Nxp, &ep, stream)) return e;
+    if (int e = clibd_gemm_bf16_nt(w.GT, 3 * Nxp, w.xT, 3 * Nxp, N, D, 3 * Nxp, &ep, nullptr, 0, stream)) return e;
     return CLIBD_OK;
 }

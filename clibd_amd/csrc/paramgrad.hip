@@ -6,7 +6,7 @@
 //   * the scatter of the embedding gradient into the word / token-type tables (autograd of nn.Embedding),
 //   * a row-range slice + bf16 cast (patch rows of the ViT token gradient, feeding the patch-embedding weight gradient).
 // All outputs ACCUMULATE (atomicAdd) into fp32 buffers the caller zeroes once per step (the flat gradient bucket).
-// Deterministic mode (the *_ordered entry points): the same kernels store one partial per block into a caller-owned workspace
+// Deterministic mode (the entry points called with a workspace): the same kernels store one partial per block into a caller-owned workspace
 // (pointer variant: ws != nullptr) and ordered_colsum_kernel (gemm.hip) adds the partials in block order; the word-table scatter
 // becomes a stable radix sort of (id, row) and fixed-order segment sums (embed_* kernels below).  No float atomics on that path.
 #include "common.h"
@@ -322,84 +322,40 @@ __global__ __launch_bounds__(256) void dropout_apply_kernel(const float* __restr
 
 using namespace clibd;
 
-extern "C" int clibd_layernorm_param_grads(const void* dy, int dy_is_f32, int ld_dy, const float* x, const float* stats, int M, int H,
-                                           float* dgamma, float* dbeta, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream) {
-    if (!dy || !x || !stats || !dgamma || !dbeta) return set_error(CLIBD_EINVAL, "layernorm_param_grads: null pointer");
-    if (M <= 0 || H <= 0 || H > 1024 || ld_dy < H) return set_error(CLIBD_EINVAL, "layernorm_param_grads: bad shape (H <= 1024)");
-    const dim3 grid((M + PG_ROWS - 1) / PG_ROWS);
-    if (dy_is_f32)
-        hipLaunchKernelGGL(ln_param_grads_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy, ld_dy, x, stats, M, H,
-                           dgamma, dbeta, drop_seed, drop_thr16, drop_scale, (float*)nullptr);
-    else
-        hipLaunchKernelGGL(ln_param_grads_kernel<unsigned short>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)dy, ld_dy, x,
-                           stats, M, H, dgamma, dbeta, drop_seed, drop_thr16, drop_scale, (float*)nullptr);
-    return check_launch("layernorm_param_grads");
-}
-
-extern "C" int clibd_batch_sum_f32(const float* x, int B, size_t R, float* out, void* stream) {
-    if (!x || !out || B <= 0 || R == 0) return set_error(CLIBD_EINVAL, "batch_sum: bad args");
-    const int chunks = B >= 64 ? 8 : 1;
-    const int bchunk = (B + chunks - 1) / chunks;
-    const size_t gx = (R + 255) / 256;
-    if (gx > 0x7fffffffull) return set_error(CLIBD_EINVAL, "batch_sum: R too large");
-    hipLaunchKernelGGL(batch_sum_kernel, dim3((unsigned)gx, (unsigned)((B + bchunk - 1) / bchunk)), dim3(256), 0, (hipStream_t)stream, x, B, R,
-                       out, bchunk, (float*)nullptr);
-    return check_launch("batch_sum");
-}
-
-extern "C" int clibd_bert_embed_bwd(const int64_t* ids, const int64_t* token_type, const float* de, int M, int H, int vocab, int type_vocab,
-                                    float* dword, float* dtype, void* stream) {
-    if (!ids || !de || (!dword && !dtype)) return set_error(CLIBD_EINVAL, "bert_embed_bwd: null pointer");
-    if (M <= 0 || H <= 0 || H > 1024 || vocab <= 0 || type_vocab <= 0) return set_error(CLIBD_EINVAL, "bert_embed_bwd: bad shape (H <= 1024)");
-    hipLaunchKernelGGL(bert_embed_bwd_kernel, dim3((M + PG_ROWS - 1) / PG_ROWS), dim3(256), 0, (hipStream_t)stream, (const long long*)ids,
-                       (const long long*)token_type, de, M, H, vocab, type_vocab, dword, dtype, (float*)nullptr);
-    return check_launch("bert_embed_bwd");
-}
-
-extern "C" int clibd_slice_rows_cast_bf16(const float* x, int B, int S, int H, int s0, int s1, void* out, void* stream) {
-    if (!x || !out || B <= 0 || S <= 0 || H <= 0 || (H & 1) || s0 < 0 || s1 > S || s0 >= s1) return set_error(CLIBD_EINVAL, "slice_rows_cast: bad args");
-    if (!aligned16(x) || !aligned16(out)) return set_error(CLIBD_EINVAL, "slice_rows_cast: alignment");
-    hipLaunchKernelGGL(slice_rows_cast_kernel, dim3(grid_for((size_t)B * (s1 - s0) * (H / 2))), dim3(256), 0, (hipStream_t)stream, x, B, S, H,
-                       s0, s1, (unsigned short*)out);
-    return check_launch("slice_rows_cast");
-}
-
-extern "C" int clibd_dropout_apply_f32(const float* x, size_t n, float* y, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream) {
-    if (!x || !y || n == 0 || n >= (1ull << 32)) return set_error(CLIBD_EINVAL, "dropout_apply: bad args (n < 2^32)");
-    if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "dropout_apply: bad dropout threshold");
-    hipLaunchKernelGGL(dropout_apply_kernel, dim3(grid_for((n + 1) / 2)), dim3(256), 0, (hipStream_t)stream, x, n, y, drop_seed,
-                       (unsigned)drop_thr16, drop_scale);
-    return check_launch("dropout_apply");
-}
-
-// ---- deterministic mode: partials workspaces instead of float atomics (see the header of this file) --------------------------------------
+// ---- the reductions: one entry point each.  NULL workspace: float atomics; with a workspace (deterministic mode, see the header of this
+// file) the same kernel stores one partial per block / chunk and ordered_colsum_kernel adds them in a fixed order.
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr int PG_ORDERED_BLOCKS = 1024;   // cap of the partial count of the row-chunk kernels (grid-stride beyond it)
 constexpr int TT_ORDERED_BLOCKS = 512;
+// blocks of a row-chunk kernel: one per PG_ROWS rows in the atomic form, capped where every block owns a workspace row
+static inline int row_chunk_blocks(int M, bool ws, int cap) {
+    const int blocks = (M + PG_ROWS - 1) / PG_ROWS;
+    return ws ? min(blocks, cap) : blocks;
+}
 
 extern "C" size_t clibd_layernorm_param_grads_workspace_bytes(int M, int H) {
     if (M <= 0 || H <= 0) return 0;
-    const int blocks = min((M + PG_ROWS - 1) / PG_ROWS, PG_ORDERED_BLOCKS);
-    return (size_t)blocks * 2 * (size_t)H * sizeof(float);
+    return (size_t)row_chunk_blocks(M, true, PG_ORDERED_BLOCKS) * 2 * (size_t)H * sizeof(float);
 }
 
-extern "C" int clibd_layernorm_param_grads_ordered(const void* dy, int dy_is_f32, int ld_dy, const float* x, const float* stats, int M, int H,
-                                                   float* dgamma, float* dbeta, uint32_t drop_seed, int drop_thr16, float drop_scale,
-                                                   void* workspace, size_t workspace_bytes, void* stream) {
-    if (!dy || !x || !stats || !dgamma || !dbeta || !workspace) return set_error(CLIBD_EINVAL, "layernorm_param_grads_ordered: null pointer");
-    if (M <= 0 || H <= 0 || H > 1024 || ld_dy < H) return set_error(CLIBD_EINVAL, "layernorm_param_grads_ordered: bad shape (H <= 1024)");
-    if (!aligned16(workspace) || workspace_bytes < clibd_layernorm_param_grads_workspace_bytes(M, H))
-        return set_error(CLIBD_EINVAL, "layernorm_param_grads_ordered: workspace too small or misaligned (clibd_layernorm_param_grads_workspace_bytes)");
-    const int blocks = min((M + PG_ROWS - 1) / PG_ROWS, PG_ORDERED_BLOCKS);
+extern "C" int clibd_layernorm_param_grads(const void* dy, int dy_is_f32, int ld_dy, const float* x, const float* stats, int M, int H,
+                                           float* dgamma, float* dbeta, uint32_t drop_seed, int drop_thr16, float drop_scale,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+    if (!dy || !x || !stats || !dgamma || !dbeta) return set_error(CLIBD_EINVAL, "layernorm_param_grads: null pointer");
+    if (M <= 0 || H <= 0 || H > 1024 || ld_dy < H) return set_error(CLIBD_EINVAL, "layernorm_param_grads: bad shape (H <= 1024)");
+    if (int e = check_workspace("layernorm_param_grads", "workspace", workspace, workspace_bytes, clibd_layernorm_param_grads_workspace_bytes(M, H),
+                                "clibd_layernorm_param_grads_workspace_bytes"))
+        return e;
     float* ws = (float*)workspace;
+    const int blocks = row_chunk_blocks(M, ws != nullptr, PG_ORDERED_BLOCKS);
     if (dy_is_f32)
         hipLaunchKernelGGL(ln_param_grads_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)dy, ld_dy, x, stats, M, H,
                            dgamma, dbeta, drop_seed, drop_thr16, drop_scale, ws);
     else
         hipLaunchKernelGGL(ln_param_grads_kernel<unsigned short>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)dy, ld_dy, x,
                            stats, M, H, dgamma, dbeta, drop_seed, drop_thr16, drop_scale, ws);
-    if (int e = check_launch("layernorm_param_grads_ordered")) return e;
-    return ordered_colsum_launch(ws, blocks, 2 * H, dgamma, H, dbeta, (hipStream_t)stream);
+    if (int e = check_launch("layernorm_param_grads")) return e;
+    return ws ? ordered_colsum_launch(ws, blocks, 2 * H, dgamma, H, dbeta, (hipStream_t)stream) : CLIBD_OK;
 }
 
 static inline int batch_chunks(int B) { return B >= 64 ? 8 : 1; }
@@ -409,24 +365,25 @@ extern "C" size_t clibd_batch_sum_workspace_bytes(int B, size_t R) {
     return (size_t)batch_chunks(B) * R * sizeof(float);
 }
 
-extern "C" int clibd_batch_sum_f32_ordered(const float* x, int B, size_t R, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !out || !workspace || B <= 0 || R == 0) return set_error(CLIBD_EINVAL, "batch_sum_ordered: bad args");
-    if (R > 0x7fffffffull) return set_error(CLIBD_EINVAL, "batch_sum_ordered: R too large");
-    if (!aligned16(workspace) || workspace_bytes < clibd_batch_sum_workspace_bytes(B, R))
-        return set_error(CLIBD_EINVAL, "batch_sum_ordered: workspace too small or misaligned (clibd_batch_sum_workspace_bytes)");
+extern "C" int clibd_batch_sum_f32(const float* x, int B, size_t R, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !out || B <= 0 || R == 0) return set_error(CLIBD_EINVAL, "batch_sum: bad args");
+    // the grid's x dimension in both forms; the fixed-order second kernel takes R as an int
+    if ((workspace ? R : (R + 255) / 256) > 0x7fffffffull) return set_error(CLIBD_EINVAL, "batch_sum: R too large");
+    if (int e = check_workspace("batch_sum", "workspace", workspace, workspace_bytes, clibd_batch_sum_workspace_bytes(B, R), "clibd_batch_sum_workspace_bytes"))
+        return e;
     const int chunks = batch_chunks(B);
     const int bchunk = (B + chunks - 1) / chunks;
     const int nchunk = (B + bchunk - 1) / bchunk;
     hipLaunchKernelGGL(batch_sum_kernel, dim3((unsigned)((R + 255) / 256), (unsigned)nchunk), dim3(256), 0, (hipStream_t)stream, x, B, R, out, bchunk,
                        (float*)workspace);
-    if (int e = check_launch("batch_sum_ordered")) return e;
-    return ordered_colsum_launch((const float*)workspace, nchunk, (int)R, out, (int)R, nullptr, (hipStream_t)stream);
+    if (int e = check_launch("batch_sum")) return e;
+    return workspace ? ordered_colsum_launch((const float*)workspace, nchunk, (int)R, out, (int)R, nullptr, (hipStream_t)stream) : CLIBD_OK;
 }
 
 struct EmbedWs { int *ka, *va, *kb, *vb, *hist; float *head, *own, *tt; size_t bytes; };
 static EmbedWs embed_ws_layout(char* base, int M, int H, int type_vocab) {
     const int ntiles = (M + EMB_TILE - 1) / EMB_TILE, nchunks = (M + EMB_CHUNK - 1) / EMB_CHUNK;
-    const int ttb = min((M + PG_ROWS - 1) / PG_ROWS, TT_ORDERED_BLOCKS);
+    const int ttb = row_chunk_blocks(M, true, TT_ORDERED_BLOCKS);
     EmbedWs w{};
     size_t o = 0;
     auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += al256(b); return p; };
@@ -444,20 +401,27 @@ extern "C" size_t clibd_bert_embed_bwd_workspace_bytes(int M, int H, int vocab, 
     return embed_ws_layout(nullptr, M, H, type_vocab).bytes;
 }
 
-extern "C" int clibd_bert_embed_bwd_ordered(const int64_t* ids, const int64_t* token_type, const float* de, int M, int H, int vocab, int type_vocab,
-                                            float* dword, float* dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!ids || !de || (!dword && !dtype) || !workspace) return set_error(CLIBD_EINVAL, "bert_embed_bwd_ordered: null pointer");
-    if (M <= 0 || H <= 0 || H > 1024 || vocab <= 0 || type_vocab <= 0) return set_error(CLIBD_EINVAL, "bert_embed_bwd_ordered: bad shape (H <= 1024)");
-    if (vocab > (1 << 24) || type_vocab > 2) return set_error(CLIBD_EINVAL, "bert_embed_bwd_ordered: vocabulary <= 2^24 and at most two token types");
-    if (!aligned16(workspace) || workspace_bytes < clibd_bert_embed_bwd_workspace_bytes(M, H, vocab, type_vocab))
-        return set_error(CLIBD_EINVAL, "bert_embed_bwd_ordered: workspace too small or misaligned (clibd_bert_embed_bwd_workspace_bytes)");
+extern "C" int clibd_bert_embed_bwd(const int64_t* ids, const int64_t* token_type, const float* de, int M, int H, int vocab, int type_vocab,
+                                    float* dword, float* dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!ids || !de || (!dword && !dtype)) return set_error(CLIBD_EINVAL, "bert_embed_bwd: null pointer");
+    if (M <= 0 || H <= 0 || H > 1024 || vocab <= 0 || type_vocab <= 0) return set_error(CLIBD_EINVAL, "bert_embed_bwd: bad shape (H <= 1024)");
+    if (workspace && (vocab > (1 << 24) || type_vocab > 2))
+        return set_error(CLIBD_EINVAL, "bert_embed_bwd: with a workspace, vocabulary <= 2^24 and at most two token types");
+    if (int e = check_workspace("bert_embed_bwd", "workspace", workspace, workspace_bytes, clibd_bert_embed_bwd_workspace_bytes(M, H, vocab, type_vocab),
+                                "clibd_bert_embed_bwd_workspace_bytes"))
+        return e;
     hipStream_t st = (hipStream_t)stream;
+    if (!workspace) {   // both tables in one pass, float atomics
+        hipLaunchKernelGGL(bert_embed_bwd_kernel, dim3(row_chunk_blocks(M, false, 0)), dim3(256), 0, st, (const long long*)ids,
+                           (const long long*)token_type, de, M, H, vocab, type_vocab, dword, dtype, (float*)nullptr);
+        return check_launch("bert_embed_bwd");
+    }
     EmbedWs w = embed_ws_layout((char*)workspace, M, H, type_vocab);
     if (dtype) {
-        const int ttb = min((M + PG_ROWS - 1) / PG_ROWS, TT_ORDERED_BLOCKS);
+        const int ttb = row_chunk_blocks(M, true, TT_ORDERED_BLOCKS);
         hipLaunchKernelGGL(bert_embed_bwd_kernel, dim3(ttb), dim3(256), 0, st, (const long long*)ids, (const long long*)token_type, de, M, H, vocab,
                            type_vocab, (float*)nullptr, dtype, w.tt);
-        if (int e = check_launch("bert_embed_bwd_ordered (token types)")) return e;
+        if (int e = check_launch("bert_embed_bwd (token types)")) return e;
         if (int e = ordered_colsum_launch(w.tt, ttb, type_vocab * H, dtype, type_vocab * H, nullptr, st)) return e;
     }
     if (!dword) return CLIBD_OK;
@@ -471,8 +435,24 @@ extern "C" int clibd_bert_embed_bwd_ordered(const int64_t* ids, const int64_t* t
         int* t = kin; kin = kout; kout = t;
         t = vin; vin = vout; vout = t;
     }
-    if (int e = check_launch("bert_embed_bwd_ordered (sort)")) return e;
+    if (int e = check_launch("bert_embed_bwd (sort)")) return e;
     hipLaunchKernelGGL(embed_chunk_sum_kernel, dim3(nchunks), dim3(256), 0, st, kin, vin, de, M, H, dword, w.head, w.own);
     hipLaunchKernelGGL(embed_join_kernel, dim3(nchunks), dim3(256), 0, st, kin, M, H, w.head, w.own, dword);
-    return check_launch("bert_embed_bwd_ordered (sums)");
+    return check_launch("bert_embed_bwd (sums)");
+}
+
+extern "C" int clibd_slice_rows_cast_bf16(const float* x, int B, int S, int H, int s0, int s1, void* out, void* stream) {
+    if (!x || !out || B <= 0 || S <= 0 || H <= 0 || (H & 1) || s0 < 0 || s1 > S || s0 >= s1) return set_error(CLIBD_EINVAL, "slice_rows_cast: bad args");
+    if (!aligned16(x) || !aligned16(out)) return set_error(CLIBD_EINVAL, "slice_rows_cast: alignment");
+    hipLaunchKernelGGL(slice_rows_cast_kernel, dim3(grid_for((size_t)B * (s1 - s0) * (H / 2))), dim3(256), 0, (hipStream_t)stream, x, B, S, H,
+                       s0, s1, (unsigned short*)out);
+    return check_launch("slice_rows_cast");
+}
+
+extern "C" int clibd_dropout_apply_f32(const float* x, size_t n, float* y, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream) {
+    if (!x || !y || n == 0 || n >= (1ull << 32)) return set_error(CLIBD_EINVAL, "dropout_apply: bad args (n < 2^32)");
+    if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "dropout_apply: bad dropout threshold");
+    hipLaunchKernelGGL(dropout_apply_kernel, dim3(grid_for((n + 1) / 2)), dim3(256), 0, (hipStream_t)stream, x, n, y, drop_seed,
+                       (unsigned)drop_thr16, drop_scale);
+    return check_launch("dropout_apply");
 }

@@ -78,20 +78,28 @@ def derive_seed(base: int, layer: int, site: int) -> int:
 # Measured in-step (profiles/r06_exp_gemm_stream_k_tail.log): 1.8-2.4 % SLOWER at per-GPU batch 256, 0.4-0.7 % slower at 2048 -> off by default (CLIBD_GEMM_STREAMK=1 turns it on)
 _STREAMK = os.environ.get("CLIBD_GEMM_STREAMK", "0") == "1"
 _TAIL_WS_BYTES = 48 * 1024 * 1024 + 1024
-_tail_ws: dict = {}
 
-# Deterministic mode (the `ordered=True` keyword of the reductions below): partials workspaces, one per (purpose, device, stream), grown on demand.
-# A workspace is only ever used by launches on its own stream, so stream order keeps consecutive users apart.
-_ordered_ws: dict = {}
+# Every workspace the C ABI takes: uint8 buffers, one per (kind, device, stream), grown on demand.  A workspace is only ever used by launches on
+# its own stream, so stream order keeps consecutive users apart.  Kinds: "tail" (stream-K tail of gemm_nt: zero-filled when created, every launch
+# leaves it zero), "splitk" (split-K partial tiles, shared by the TN and NT weight-gradient paths), and one per reduction of the deterministic
+# mode (the `ordered=True` keyword below).
+_workspaces: dict = {"tail": {}}   # kind -> {(device, stream): buffer}
+_tail_ws = _workspaces["tail"]
 
 
-def _ordered_workspace(kind: str, nbytes: int, device) -> torch.Tensor:
-    key = (kind, device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _ordered_ws.get(key)
+def _workspace(kind: str, nbytes: int, device, zero: bool = False) -> torch.Tensor:
+    cache = _workspaces.setdefault(kind, {})
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = cache.get(key)
     if ws is None or ws.numel() < nbytes:
-        ws = torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
-        _ordered_ws[key] = ws
+        ws = (torch.zeros if zero else torch.empty)(((max(int(nbytes), 16) + 15) // 16 * 16,), dtype=torch.uint8, device=device)
+        cache[key] = ws
     return ws
+
+
+def _ws_args(ws: Optional[torch.Tensor]) -> tuple:
+    """(workspace, workspace_bytes) of the C ABI; no workspace: (None, 0), the atomic / plain form"""
+    return (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
 
 
 def _not_ordered(what: str):
@@ -187,17 +195,12 @@ def gemm_nt(
     lib = _lib.load()
     # Stream-K tail (round 6): launches whose last tile round is at most half full and whose contraction is long take a per-(device, stream) workspace
     # (zeroed once; 48 MiB + 1 KiB covers every shape) and cut that round's tiles into K-slices over the idle CUs.  Opt-in: see _STREAMK.
+    ws = None
     if _STREAMK and split_k == 1 and M >= 1024:
         need = int(lib.clibd_gemm_tail_workspace_bytes(M, N, K))
         if need > 0:
-            key = (a.device, torch.cuda.current_stream(a.device).cuda_stream)
-            ws = _tail_ws.get(key)
-            if ws is None or ws.numel() < need:
-                ws = torch.zeros((max(need, _TAIL_WS_BYTES),), dtype=torch.uint8, device=a.device)
-                _tail_ws[key] = ws
-            check(lib.clibd_gemm_bf16_nt_ws(a.data_ptr(), lda, w.data_ptr(), ldw, M, N, K, C.byref(ep), ws.data_ptr(), ws.numel(), _stream()), "gemm_bf16_nt_ws")
-            return
-    check(lib.clibd_gemm_bf16_nt(a.data_ptr(), lda, w.data_ptr(), ldw, M, N, K, C.byref(ep), _stream()), "gemm_bf16_nt")
+            ws = _workspace("tail", max(need, _TAIL_WS_BYTES), a.device, zero=True)
+    check(lib.clibd_gemm_bf16_nt(a.data_ptr(), lda, w.data_ptr(), ldw, M, N, K, C.byref(ep), *_ws_args(ws), _stream()), "gemm_bf16_nt")
 
 
 def rowsum_finalize(row_sums: torch.Tensor, eps: float, stats: torch.Tensor) -> None:
@@ -373,7 +376,7 @@ def gemm_fp8_nt(
 def transpose_bf16(x: torch.Tensor, pad_to: int = 64, colsum: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[R,C] bf16 -> [C, R_pad] bf16 (zero padded along R to a multiple of `pad_to`).
     colsum (fp32 [C], accumulates): column sums of x in the same pass (bias gradient beside the weight gradient's dy^T), through a
-    partials workspace and a fixed-order second kernel (clibd_transpose_colsum_bf16_ws: no float atomics, bit-reproducible)."""
+    partials workspace and a fixed-order second kernel (always: no float atomics, bit-reproducible)."""
     _chk(x, BF16, "x", contiguous=False)
     ld = _rowmajor(x, "x")
     R, Cc = x.shape
@@ -386,8 +389,8 @@ def transpose_bf16(x: torch.Tensor, pad_to: int = 64, colsum: Optional[torch.Ten
         lib = _lib.load()
         need = int(lib.clibd_transpose_colsum_workspace_bytes(Rp, Cc))
         ws = torch.empty(((need + 3) // 4,), dtype=F32, device=x.device)
-        check(lib.clibd_transpose_colsum_bf16_ws(x.data_ptr(), ld, R, Cc, out.data_ptr(), Rp, colsum.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream()),
-              "transpose_colsum_bf16_ws")
+        check(lib.clibd_transpose_colsum_bf16(x.data_ptr(), ld, R, Cc, out.data_ptr(), Rp, colsum.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream()),
+              "transpose_colsum_bf16")
     else:
         check(_lib.load().clibd_transpose_bf16(x.data_ptr(), ld, R, Cc, out.data_ptr(), Rp, _stream()), "transpose_bf16")
     return out
@@ -469,11 +472,11 @@ def layernorm_bwd(dy, x, stats, gamma, *, dres=None, dx_f32=None, dx_bf16=None, 
     if dx_f32 is None and dx_bf16 is None and dx_res_bf16 is None and dx_fp8 is None:
         raise ValueError("layernorm_bwd: no output")
     lib = _lib.load()
-    ws = _ordered_workspace("ln_pg", int(lib.clibd_layernorm_bwd_pg_workspace_bytes(M, H)), x.device) if ordered and dgamma is not None else None
+    ws = _workspace("ln_pg", int(lib.clibd_layernorm_bwd_pg_workspace_bytes(M, H)), x.device) if ordered and dgamma is not None else None
     dyb, dyf = (dy.data_ptr(), None) if dy.dtype == BF16 else (None, dy.data_ptr())
     check(lib.clibd_layernorm_bwd(dyb, dyf, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), M, H, _p(dres), _p(dres_bf16), _p(dx_f32),
                                   _p(dx_res_bf16), _p(dx_bf16), *_drop_args(drop), _p(dx_fp8), _p(row_dequant), _p(dgamma), _p(dbeta),
-                                  _p(ws), 0 if ws is None else ws.numel(), _stream()), "layernorm_bwd")
+                                  *_ws_args(ws), _stream()), "layernorm_bwd")
 
 
 def attention_fwd(qkv: torch.Tensor, B: int, S: int, nheads: int, key_mask: Optional[torch.Tensor], out: torch.Tensor,
@@ -713,16 +716,13 @@ def token_mean_bwd(dout: torch.Tensor, S: int) -> torch.Tensor:
 
 
 def colsum_bf16(x: torch.Tensor, out: torch.Tensor, ordered: bool = False) -> None:
-    """out[N] (fp32) += column sums of x[M,N] (bf16).  ordered: per-chunk partials summed in chunk order (clibd_colsum_bf16_ordered)."""
+    """out[N] (fp32) += column sums of x[M,N] (bf16).  ordered: per-chunk partials summed in chunk order."""
     _chk(x, BF16, "x", contiguous=False)
     _chk(out, F32, "out")
     M, N = x.shape
-    if ordered:
-        lib = _lib.load()
-        ws = _ordered_workspace("colsum", int(lib.clibd_colsum_workspace_bytes(M, N)), x.device)
-        check(lib.clibd_colsum_bf16_ordered(x.data_ptr(), _rowmajor(x, "x"), M, N, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "colsum_bf16_ordered")
-        return
-    check(_lib.load().clibd_colsum_bf16(x.data_ptr(), _rowmajor(x, "x"), M, N, out.data_ptr(), _stream()), "colsum_bf16")
+    lib = _lib.load()
+    ws = _workspace("colsum", int(lib.clibd_colsum_workspace_bytes(M, N)), x.device) if ordered else None
+    check(lib.clibd_colsum_bf16(x.data_ptr(), _rowmajor(x, "x"), M, N, out.data_ptr(), *_ws_args(ws), _stream()), "colsum_bf16")
 
 
 def gather_rows(x: torch.Tensor) -> torch.Tensor:
@@ -1023,16 +1023,10 @@ def layernorm_param_grads(dy: torch.Tensor, x: torch.Tensor, stats: torch.Tensor
     M, H = x.shape
     if tuple(dy.shape) != (M, H) or stats.numel() != 2 * M or dgamma.numel() != H or dbeta.numel() != H:
         raise ValueError("layernorm_param_grads: shape mismatch")
-    d = _drop_args(drop)
-    if ordered:
-        lib = _lib.load()
-        ws = _ordered_workspace("ln_param", int(lib.clibd_layernorm_param_grads_workspace_bytes(M, H)), x.device)
-        check(lib.clibd_layernorm_param_grads_ordered(dy.data_ptr(), int(dy.dtype == F32), _rowmajor(dy, "dy"), x.data_ptr(), stats.data_ptr(), M, H,
-                                                      dgamma.data_ptr(), dbeta.data_ptr(), *d, ws.data_ptr(), ws.numel(), _stream()),
-              "layernorm_param_grads_ordered")
-        return
-    check(_lib.load().clibd_layernorm_param_grads(dy.data_ptr(), int(dy.dtype == F32), _rowmajor(dy, "dy"), x.data_ptr(), stats.data_ptr(), M, H,
-                                                  dgamma.data_ptr(), dbeta.data_ptr(), *d, _stream()), "layernorm_param_grads")
+    lib = _lib.load()
+    ws = _workspace("ln_param", int(lib.clibd_layernorm_param_grads_workspace_bytes(M, H)), x.device) if ordered else None
+    check(lib.clibd_layernorm_param_grads(dy.data_ptr(), int(dy.dtype == F32), _rowmajor(dy, "dy"), x.data_ptr(), stats.data_ptr(), M, H,
+                                          dgamma.data_ptr(), dbeta.data_ptr(), *_drop_args(drop), *_ws_args(ws), _stream()), "layernorm_param_grads")
 
 
 def batch_sum(x: torch.Tensor, out: torch.Tensor, ordered: bool = False) -> None:
@@ -1042,21 +1036,16 @@ def batch_sum(x: torch.Tensor, out: torch.Tensor, ordered: bool = False) -> None
     R = x.numel() // B
     if out.numel() != R:
         raise ValueError("batch_sum: out must have x.numel() / B elements")
-    if ordered:
-        if not out.is_contiguous():
-            raise ValueError("batch_sum: out must be contiguous")
-        lib = _lib.load()
-        ws = _ordered_workspace("batch_sum", int(lib.clibd_batch_sum_workspace_bytes(B, R)), x.device)
-        check(lib.clibd_batch_sum_f32_ordered(x.data_ptr(), B, R, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "batch_sum_ordered")
-        return
-    check(_lib.load().clibd_batch_sum_f32(x.data_ptr(), B, R, out.data_ptr(), _stream()), "batch_sum")
+    lib = _lib.load()
+    ws = _workspace("batch_sum", int(lib.clibd_batch_sum_workspace_bytes(B, R)), x.device) if ordered else None
+    check(lib.clibd_batch_sum_f32(x.data_ptr(), B, R, out.data_ptr(), *_ws_args(ws), _stream()), "batch_sum")
 
 
 def bert_embed_bwd(ids: torch.Tensor, token_type: Optional[torch.Tensor], de: torch.Tensor, dword: Optional[torch.Tensor],
                    dtype_table: Optional[torch.Tensor], ordered: bool = False) -> None:
     """Scatter the embedding gradient de [M,H] into the word table (by ids) and the token-type table (accumulating).
     ordered: the word table through a stable sort of (id, row) and per-id sums in row order, the token-type table (at most two types)
-    through per-block partials (clibd_bert_embed_bwd_ordered)."""
+    through per-block partials."""
     _chk(ids, torch.int64, "ids"); _chk(de, F32, "de")
     M, H = de.shape
     if ids.numel() != M:
@@ -1068,16 +1057,12 @@ def bert_embed_bwd(ids: torch.Tensor, token_type: Optional[torch.Tensor], de: to
     for t, n in ((dword, "dword"), (dtype_table, "dtype")):
         if t is not None:
             _chk(t, F32, n)
-    if ordered:
-        if tv > 2:
-            raise _not_ordered(f"bert_embed_bwd with {tv} token types")
-        lib = _lib.load()
-        ws = _ordered_workspace("embed", int(lib.clibd_bert_embed_bwd_workspace_bytes(M, H, vocab, tv)), de.device)
-        check(lib.clibd_bert_embed_bwd_ordered(ids.data_ptr(), _p(token_type), de.data_ptr(), M, H, vocab, tv, _p(dword), _p(dtype_table),
-                                               ws.data_ptr(), ws.numel(), _stream()), "bert_embed_bwd_ordered")
-        return
-    check(_lib.load().clibd_bert_embed_bwd(ids.data_ptr(), _p(token_type), de.data_ptr(), M, H, vocab, tv, _p(dword), _p(dtype_table), _stream()),
-          "bert_embed_bwd")
+    if ordered and tv > 2:
+        raise _not_ordered(f"bert_embed_bwd with {tv} token types")
+    lib = _lib.load()
+    ws = _workspace("embed", int(lib.clibd_bert_embed_bwd_workspace_bytes(M, H, vocab, tv)), de.device) if ordered else None
+    check(lib.clibd_bert_embed_bwd(ids.data_ptr(), _p(token_type), de.data_ptr(), M, H, vocab, tv, _p(dword), _p(dtype_table), *_ws_args(ws),
+                                   _stream()), "bert_embed_bwd")
 
 
 def slice_rows_cast_bf16(x: torch.Tensor, s0: int, s1: int) -> torch.Tensor:
@@ -1095,9 +1080,6 @@ def dropout_apply(x: torch.Tensor, drop: Drop) -> torch.Tensor:
     y = torch.empty_like(x)
     check(_lib.load().clibd_dropout_apply_f32(x.data_ptr(), x.numel(), y.data_ptr(), drop.seed, drop.thr16, drop.scale, _stream()), "dropout_apply")
     return y
-
-
-_splitk_ws = {}
 
 
 def gemm_tn_splitk(a: torch.Tensor, b: torch.Tensor, out_f32: torch.Tensor, accumulate: bool = True, colsum: Optional[torch.Tensor] = None,
@@ -1123,40 +1105,19 @@ def gemm_tn_splitk(a: torch.Tensor, b: torch.Tensor, out_f32: torch.Tensor, accu
         raise ValueError("gemm_tn_splitk: shape mismatch")
     if M % 128 or M < 256 or Na % 256 or Nb % 256:
         return False
-    lib = _lib.load()
-    need = lib.clibd_gemm_splitk_workspace_bytes(Na, Nb)
-    key = (a.device, torch.cuda.current_stream(a.device).cuda_stream)
-    ws = _splitk_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty(((need + 3) // 4,), dtype=F32, device=a.device)   # one workspace per (device, stream), shared with the NT mode
-        _splitk_ws[key] = ws
     if colsum is not None:
         _chk(colsum, F32, "colsum")
         if colsum.numel() != Na:
             raise ValueError("gemm_tn_splitk: colsum must have Na elements")
-    if b8:
-        if ordered and colsum is not None:
-            cws = _ordered_workspace("tn_colsum", int(lib.clibd_gemm_tn_colsum_workspace_bytes(M, Na)), a.device)
-            rc = lib.clibd_gemm_fp8b_tn_splitk_ordered(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), float(b_scale), M, Na, Nb,
-                                                       out_f32.data_ptr(), Nb, int(accumulate), colsum.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                                       cws.data_ptr(), cws.numel(), _stream())
-        else:
-            rc = lib.clibd_gemm_fp8b_tn_splitk(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), float(b_scale), M, Na, Nb,
-                                               out_f32.data_ptr(), Nb, int(accumulate), _p(colsum), ws.data_ptr(), ws.numel() * 4, _stream())
-        if rc != 0 and b"shape not supported" in (lib.clibd_last_error() or b""):
-            return False
-        check(rc, "gemm_fp8b_tn_splitk")
-        return True
-    if ordered and colsum is not None:
-        cws = _ordered_workspace("tn_colsum", int(lib.clibd_gemm_tn_colsum_workspace_bytes(M, Na)), a.device)
-        rc = lib.clibd_gemm_bf16_tn_splitk_ordered(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), M, Na, Nb, out_f32.data_ptr(), Nb,
-                                                   int(accumulate), colsum.data_ptr(), ws.data_ptr(), ws.numel() * 4, cws.data_ptr(), cws.numel(), _stream())
-    else:
-        rc = lib.clibd_gemm_bf16_tn_splitk(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), M, Na, Nb, out_f32.data_ptr(), Nb,
-                                           int(accumulate), _p(colsum), ws.data_ptr(), ws.numel() * 4, _stream())
+    lib = _lib.load()
+    ws = _workspace("splitk", int(lib.clibd_gemm_splitk_workspace_bytes(Na, Nb)), a.device)   # shared with the NT mode
+    cws = _workspace("tn_colsum", int(lib.clibd_gemm_tn_colsum_workspace_bytes(M, Na)), a.device) if ordered and colsum is not None else None
+    fn, scale = (lib.clibd_gemm_fp8b_tn_splitk, (float(b_scale),)) if b8 else (lib.clibd_gemm_bf16_tn_splitk, ())
+    rc = fn(a.data_ptr(), _rowmajor(a, "a"), b.data_ptr(), _rowmajor(b, "b"), *scale, M, Na, Nb, out_f32.data_ptr(), Nb, int(accumulate), _p(colsum),
+            *_ws_args(ws), *_ws_args(cws), _stream())
     if rc != 0 and b"shape not supported" in (lib.clibd_last_error() or b""):
         return False    # declined before anything was enqueued: the caller takes the transpose + NT path
-    check(rc, "gemm_bf16_tn_splitk")
+    check(rc, "gemm_fp8b_tn_splitk" if b8 else "gemm_bf16_tn_splitk")
     return True
 
 
@@ -1171,14 +1132,9 @@ def gemm_nt_splitk(a: torch.Tensor, w: torch.Tensor, out_f32: torch.Tensor, accu
     if N % 256 or K % 128 or K < 512:
         return False
     lib = _lib.load()
-    need = lib.clibd_gemm_splitk_workspace_bytes(M, N)
-    key = (a.device, torch.cuda.current_stream(a.device).cuda_stream)
-    ws = _splitk_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty(((need + 3) // 4,), dtype=F32, device=a.device)   # one workspace per (device, stream)
-        _splitk_ws[key] = ws
+    ws = _workspace("splitk", int(lib.clibd_gemm_splitk_workspace_bytes(M, N)), a.device)   # shared with the TN mode
     rc = lib.clibd_gemm_bf16_nt_splitk(a.data_ptr(), _rowmajor(a, "a"), w.data_ptr(), _rowmajor(w, "w"), M, N, K, out_f32.data_ptr(), N,
-                                       int(accumulate), ws.data_ptr(), ws.numel() * 4, _stream())
+                                       int(accumulate), *_ws_args(ws), _stream())
     if rc != 0 and b"shape not supported" in (lib.clibd_last_error() or b""):
         return False    # declined before anything was enqueued: the caller uses gemm_nt(split_k=)
     check(rc, "gemm_bf16_nt_splitk")

@@ -102,17 +102,16 @@ typedef struct clibd_gemm_epilogue {
     const float* col_sum_w;
 } clibd_gemm_epilogue;
 
-int clibd_gemm_bf16_nt(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
-                       const clibd_gemm_epilogue* ep, void* stream);
-/* ABI 5 — the same with a STREAM-K TAIL workspace.  The 256x256 kernel runs one persistent workgroup per CU; a launch whose last tile round is at most
+/* workspace (ABI 5; the workspace rule of the "deterministic mode" comment below; NULL, 0: the plain launch): the STREAM-K TAIL.  The 256x256 kernel runs
+ * one persistent workgroup per CU; a launch whose last tile round is at most
  * half full (591 tiles on 256 CUs: 79 in the third round) and whose contraction is long (K >= 1536) cuts that round's tiles into 2-4 K-slices, one per
  * otherwise idle CU: slices 1.. store fp32 partial tiles to the workspace and raise a flag, slice 0 waits, adds them in a fixed order and runs the
  * epilogue.  Results are deterministic; rows of those tiles differ from the plain launch's by fp32 summation order only.  workspace:
  * clibd_gemm_tail_workspace_bytes(M, N, K) bytes (0: this shape has no use for it; <= 48 MiB + 1 KiB), 16-byte aligned, whose first 1 KiB the caller
- * zeroes ONCE (every launch leaves it zero); one workspace per stream.  NULL workspace, or a kind without the form: the plain launch. */
+ * zeroes ONCE (every launch leaves it zero); one workspace per stream.  A shape or an epilogue kind without the form ignores it: the plain launch. */
 size_t clibd_gemm_tail_workspace_bytes(int M, int N, int K);
-int clibd_gemm_bf16_nt_ws(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
-                          const clibd_gemm_epilogue* ep, void* workspace, size_t workspace_bytes, void* stream);
+int clibd_gemm_bf16_nt(const void* A, int lda, const void* W, int ldw, int M, int N, int K,
+                       const clibd_gemm_epilogue* ep, void* workspace, size_t workspace_bytes, void* stream);
 /* Same product with the K range [hole_k0, hole_k0 + hole_len) of BOTH operands skipped (multiples of 64; 128x128 kernel):
  * for an A whose column segment meets all-zero weights — the adapters' dt projection reads the q and v segments of dqkv
  * and never touches the k segment (a third of the bytes of a latency/HBM-bound skinny product). */
@@ -167,14 +166,13 @@ int clibd_transpose_bf16(const void* in, int ld_in, int R, int C, void* out, int
  * transposed, dequantised X operand of the fp8-forward weight gradient where the rows-contracting kernel does not take the shape. */
 int clibd_transpose_fp8_bf16(const void* in, int ld_in, int R, int C, float scale, void* out, int ld_out, void* stream);
 /* same, and colsum[c] += sum_r in[r, c] (fp32, accumulates): the bias gradient of a linear layer rides along with the transpose
- * of dy that its weight gradient needs (full fine-tune mode).  Needs C, ld_in, ld_out multiples of 8, 16-byte aligned bases. */
-int clibd_transpose_colsum_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, void* stream);
-/* ABI 5 — the same with a partials workspace (clibd_transpose_colsum_workspace_bytes(ld_out, C) bytes): every row block writes its
- * column sums to the workspace and a second kernel adds them to colsum in row-block order, so the bias gradient repeats bit for bit from
- * run to run (the form above issues one float atomic per block and column).  The trainable heads of the LoRA step take this form. */
+ * of dy that its weight gradient needs (full fine-tune mode).  Needs C, ld_in, ld_out multiples of 8, 16-byte aligned bases.
+ * workspace (the workspace rule of the "deterministic mode" comment below; clibd_transpose_colsum_workspace_bytes(ld_out, C) bytes): NULL, 0: one
+ * float atomic per block and column.  Else every row block writes its column sums to the workspace and a second kernel adds them to colsum in
+ * row-block order, so the bias gradient repeats bit for bit from run to run.  The trainable heads of the LoRA step take this form. */
 size_t clibd_transpose_colsum_workspace_bytes(int ld_out, int C);
-int clibd_transpose_colsum_bf16_ws(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, void* workspace,
-                                   size_t workspace_bytes, void* stream);
+int clibd_transpose_colsum_bf16(const void* in, int ld_in, int R, int C, void* out, int ld_out, float* colsum, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 /* fp32 -> bf16 cast of a contiguous buffer (weights are kept fp32 in the state dict, bf16 shadow copies
  * feed the MFMA path, as torch.autocast does per call in the reference, epoch/train_epoch.py:43). */
@@ -342,8 +340,10 @@ int clibd_token_mean_fwd(const float* x, int B, int S, int H, void* out_bf16, vo
 int clibd_token_mean_bwd(const float* dout, int B, int S, int H, float* dx, void* stream);
 /* dx = dy * gelu'(pre), bf16 in/out, n % 4 == 0 (HF BertPredictionHeadTransform: dense -> gelu -> LayerNorm) */
 int clibd_gelu_bwd_bf16(const void* dy, const void* pre, size_t n, void* dx, void* stream);
-/* column sums of a bf16 [M,N] matrix into fp32 [N] (bias gradients of the trainable heads; accumulates) */
-int clibd_colsum_bf16(const void* x, int ld, int M, int N, float* out, void* stream);
+/* column sums of a bf16 [M,N] matrix into fp32 [N] (bias gradients of the trainable heads; accumulates).  workspace: see "deterministic
+ * mode" below (per-chunk partials, clibd_colsum_workspace_bytes). */
+size_t clibd_colsum_workspace_bytes(int M, int N);
+int clibd_colsum_bf16(const void* x, int ld, int M, int N, float* out, void* workspace, size_t workspace_bytes, void* stream);
 /* gather / scatter the [CLS] rows: x fp32 [B,S,H] row 0 <-> [B,H] */
 int clibd_gather_rows(const float* x, int B, int S, int H, float* out, void* stream);
 int clibd_scatter_rows_bf16(const float* dcls, int B, int S, int H, void* dx_bf16, float* dx_f32, void* stream);
@@ -492,66 +492,60 @@ int clibd_gemm_bf16_nt_splitk(const void* A, int lda, const void* W, int ldw, in
 
 /* The same product with both operands read in place: out[Na,Nb] (+)= A[M,Na]^T · B[M,Nb] (bf16, contraction over the token
  * rows through transposing LDS reads; the weight gradient dW = dY^T X without materialising dY^T and X^T).
- * colsum_a (optional, fp32 [Na], accumulates atomically): column sums of A in the same pass (the bias gradient db = dY^T 1).
- * M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, lda / ldb % 8 == 0; workspace >= clibd_gemm_splitk_workspace_bytes(Na, Nb). */
+ * colsum_a (optional, fp32 [Na], accumulates): column sums of A in the same pass (the bias gradient db = dY^T 1).
+ * M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, lda / ldb % 8 == 0; workspace (required) >= clibd_gemm_splitk_workspace_bytes(Na, Nb).
+ * colsum_workspace (needs colsum_a; the workspace rule of the "deterministic mode" comment below; clibd_gemm_tn_colsum_workspace_bytes(M, Na)
+ * bytes): NULL, 0: colsum_a by float atomics.  Else the column sums are stored per M-slice and summed in slice order. */
+size_t clibd_gemm_tn_colsum_workspace_bytes(int M, int Na);
 int clibd_gemm_bf16_tn_splitk(const void* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* out_f32, int ld_out,
-                              int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* stream);
-/* The same product with B as OCP e4m3 bytes and one dequantisation factor: out[Na,Nb] (+)= A[M,Na]^T · (B8[M,Nb] * b_scale) (ABI 5,
- * additive).  The weight gradient of a linear layer whose forward GEMM consumed its input as e4m3(x sa) (fp8 forward under full
+                              int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
+                              size_t colsum_workspace_bytes, void* stream);
+/* The same product with B as OCP e4m3 bytes and one dequantisation factor: out[Na,Nb] (+)= A[M,Na]^T · (B8[M,Nb] * b_scale) (ABI 5).
+ * The weight gradient of a linear layer whose forward GEMM consumed its input as e4m3(x sa) (fp8 forward under full
  * fine-tune): dW = dY^T · e4m3(x sa) / sa with b_scale = 1 / sa.  The e4m3 values are widened to bf16 exactly and b_scale multiplies
  * the fp32 tile, so for a power-of-two b_scale the result equals clibd_gemm_bf16_tn_splitk on bf16(B8 * b_scale) bit for bit.  Same
- * shapes, split plan, workspace and colsum_a as that entry point; ldb (in elements = bytes) % 8 == 0, B8 8-byte aligned, b_scale > 0.
- * The _ordered form matches clibd_gemm_bf16_tn_splitk_ordered (declared below with the deterministic mode). */
+ * shapes, split plan, workspaces and colsum_a as that entry point; ldb (in elements = bytes) % 8 == 0, B8 8-byte aligned, b_scale > 0. */
 int clibd_gemm_fp8b_tn_splitk(const void* A, int lda, const void* B8, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32,
-                              int ld_out, int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* stream);
+                              int ld_out, int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
+                              size_t colsum_workspace_bytes, void* stream);
 
 /* ---- full fine-tune mode (model_config.disable_lora): parameter gradients that are not GEMM-shaped.
- * Every output ACCUMULATES (atomicAdd) into fp32 buffers the caller zeroes once per step.
+ * Every output ACCUMULATES into fp32 buffers the caller zeroes once per step.
  * Replaces the autograd of nn.LayerNorm (timm Block.norm1/2, VisionTransformer.norm; HF Bert*LayerNorm), of nn.Embedding
- * (HF BertEmbeddings) and of the position / class-token parameters (timm VisionTransformer._pos_embed). */
+ * (HF BertEmbeddings) and of the position / class-token parameters (timm VisionTransformer._pos_embed).
+ *
+ * ---- deterministic mode (ABI 5; one entry point per reduction since ABI 7).  THE WORKSPACE RULE of every reduction that takes a
+ * (workspace, workspace_bytes) pair — the four below, clibd_colsum_bf16, clibd_transpose_colsum_bf16, the colsum_workspace of the TN split-K
+ * products, the stream-K tail of clibd_gemm_bf16_nt, and clibd_layernorm_bwd / clibd_lora_wgrad / clibd_lora_backward:
+ *   - NULL with size 0 selects the atomic form (float atomicAdd into the output; for clibd_gemm_bf16_nt the plain launch);
+ *   - NULL with a non-zero size returns CLIBD_EINVAL;
+ *   - otherwise the workspace is caller-owned, 16-byte aligned and at least as large as the entry's *_workspace_bytes query says: a misaligned or
+ *     short one returns CLIBD_EINVAL with a message that names the query.  The same kernel then writes one partial per block / slice / chunk
+ *     there and a second kernel adds the partials in a fixed order (block, slice, chunk order), so that the result depends on the inputs and the
+ *     shape only and repeats bit for bit.  Nothing allocates; everything is enqueued on `stream`; one workspace per stream.
+ * A limit that belongs to one form applies only when that form is selected. */
 /* dgamma[c] += sum_m dy[m,c] * (x[m,c]-mean[m]) * rstd[m];  dbeta[c] += sum_m dy[m,c].  dy [M,H] bf16 or fp32 (dy_is_f32),
  * row stride ld_dy; x fp32 [M,H]; stats fp32 [M,2]; drop_thr16 > 0: dy is first multiplied by the dropout factor of
- * element m*H+c (LayerNorm whose output went through dropout: HF BertEmbeddings).  H <= 1024. */
+ * element m*H+c (LayerNorm whose output went through dropout: HF BertEmbeddings).  H <= 1024.  workspace: per-block partials. */
+size_t clibd_layernorm_param_grads_workspace_bytes(int M, int H);
 int clibd_layernorm_param_grads(const void* dy, int dy_is_f32, int ld_dy, const float* x, const float* stats, int M, int H,
-                                float* dgamma, float* dbeta, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream);
+                                float* dgamma, float* dbeta, uint32_t drop_seed, int drop_thr16, float drop_scale,
+                                void* workspace, size_t workspace_bytes, void* stream);
 /* y[i] = x[i] * dropout_factor(seed, i) (x, y fp32 [n], may alias): gradient through a dropout whose mask index is the flat
  * element index (y = dropout(LN(e)) of HF BertEmbeddings, when the embedding tables are trainable). */
 int clibd_dropout_apply_f32(const float* x, size_t n, float* y, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream);
-/* out[r] += sum_b x[b, r]  (x fp32 [B, R]): position-embedding and class-token gradients. */
-int clibd_batch_sum_f32(const float* x, int B, size_t R, float* out, void* stream);
-/* dword[ids[m], :] += de[m, :];  dtype[token_type[m] (0 if NULL), :] += de[m, :]   (de fp32 [M,H]; either table may be NULL). */
+/* out[r] += sum_b x[b, r]  (x fp32 [B, R]): position-embedding and class-token gradients.  workspace: per-chunk partials (R < 2^31). */
+size_t clibd_batch_sum_workspace_bytes(int B, size_t R);
+int clibd_batch_sum_f32(const float* x, int B, size_t R, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* dword[ids[m], :] += de[m, :];  dtype[token_type[m] (0 if NULL), :] += de[m, :]   (de fp32 [M,H]; either table may be NULL).
+ * workspace (vocab <= 2^24, type_vocab <= 2; the atomic form takes any vocabulary and any number of token types): the word table through a
+ * stable radix sort of (id, row), then per-id sums in row order (long lists cut into fixed chunks whose partials are added in chunk order); the
+ * token-type table through per-block partials. */
+size_t clibd_bert_embed_bwd_workspace_bytes(int M, int H, int vocab, int type_vocab);
 int clibd_bert_embed_bwd(const int64_t* ids, const int64_t* token_type, const float* de, int M, int H, int vocab, int type_vocab,
-                         float* dword, float* dtype, void* stream);
+                         float* dword, float* dtype, void* workspace, size_t workspace_bytes, void* stream);
 /* out bf16 [B*(s1-s0), H] = rows s0..s1-1 of every sequence of x fp32 [B,S,H] (patch rows of the ViT token gradient). */
 int clibd_slice_rows_cast_bf16(const float* x, int B, int S, int H, int s0, int s1, void* out, void* stream);
-
-/* ---- deterministic mode (ABI 5, additive): the forms above without float atomics.  Each writes one partial per block / slice / chunk into
- * a caller-owned workspace (size from its *_workspace_bytes query; 16-byte aligned) and a second kernel adds the partials in a fixed order
- * (block, slice, chunk order), so that the result depends on the inputs and the shape only and repeats bit for bit.  Outputs ACCUMULATE as
- * in the atomic forms; nothing allocates; everything is enqueued on `stream`.  A null or short workspace returns -1. */
-/* (clibd_layernorm_bwd takes its workspace as an argument: declared with the LayerNorm entry points above.) */
-size_t clibd_layernorm_param_grads_workspace_bytes(int M, int H);
-int clibd_layernorm_param_grads_ordered(const void* dy, int dy_is_f32, int ld_dy, const float* x, const float* stats, int M, int H,
-                                        float* dgamma, float* dbeta, uint32_t drop_seed, int drop_thr16, float drop_scale,
-                                        void* workspace, size_t workspace_bytes, void* stream);
-size_t clibd_batch_sum_workspace_bytes(int B, size_t R);
-int clibd_batch_sum_f32_ordered(const float* x, int B, size_t R, float* out, void* workspace, size_t workspace_bytes, void* stream);
-/* word table: a stable radix sort of (id, row), then per-id sums in row order (long lists cut into fixed chunks whose partials are added
- * in chunk order); token-type table (type_vocab <= 2): per-block partials.  vocab <= 2^24. */
-size_t clibd_bert_embed_bwd_workspace_bytes(int M, int H, int vocab, int type_vocab);
-int clibd_bert_embed_bwd_ordered(const int64_t* ids, const int64_t* token_type, const float* de, int M, int H, int vocab, int type_vocab,
-                                 float* dword, float* dtype, void* workspace, size_t workspace_bytes, void* stream);
-size_t clibd_colsum_workspace_bytes(int M, int N);
-int clibd_colsum_bf16_ordered(const void* x, int ld, int M, int N, float* out, void* workspace, size_t workspace_bytes, void* stream);
-/* clibd_gemm_bf16_tn_splitk with colsum_a (required) stored per M-slice into colsum_workspace and summed in slice order. */
-size_t clibd_gemm_tn_colsum_workspace_bytes(int M, int Na);
-int clibd_gemm_bf16_tn_splitk_ordered(const void* A, int lda, const void* B, int ldb, int M, int Na, int Nb, float* out_f32, int ld_out,
-                                      int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes, void* colsum_workspace,
-                                      size_t colsum_workspace_bytes, void* stream);
-/* clibd_gemm_fp8b_tn_splitk with colsum_a (required) stored per M-slice and summed in slice order. */
-int clibd_gemm_fp8b_tn_splitk_ordered(const void* A, int lda, const void* B8, int ldb, float b_scale, int M, int Na, int Nb, float* out_f32,
-                                      int ld_out, int accumulate, float* colsum_a, void* workspace, size_t workspace_bytes,
-                                      void* colsum_workspace, size_t colsum_workspace_bytes, void* stream);
 
 /* fused AdamW step on a flat fp32 parameter bucket (torch.optim.AdamW semantics, scripts/train_cl.py:221):
  * p,g,m,v [n]; g is multiplied by grad_scale first (1/world_size folding etc.). */

@@ -38,8 +38,8 @@ def test_library_exports_every_declared_symbol(lib):
 def test_python_binding_covers_every_declared_symbol(lib):
     from clibd_amd import _lib
 
-    assert sorted(_lib.SIGNATURES) == declared_symbols()
-    assert _lib.load().clibd_abi_version() == _lib.ABI_VERSION == 6
+    assert sorted(_lib.SIGNATURES) == declared_symbols() and len(_lib.SIGNATURES) == 74
+    assert _lib.load().clibd_abi_version() == _lib.ABI_VERSION == 7
 
 
 def test_binding_refuses_a_library_built_from_other_sources(lib, monkeypatch):
@@ -69,7 +69,7 @@ def test_host_side_validation_needs_no_gpu(lib):
 
     L = _lib.load()
     ep = _lib.GemmEpilogue()
-    assert L.clibd_gemm_bf16_nt(None, 64, None, 64, 8, 16, 64, ctypes.byref(ep), None) == -1
+    assert L.clibd_gemm_bf16_nt(None, 64, None, 64, 8, 16, 64, ctypes.byref(ep), None, 0, None) == -1
     assert b"null" in L.clibd_last_error()
     assert L.clibd_attention_fwd(ctypes.c_void_p(16), 1, 300, 1, None, ctypes.c_void_p(16), 300, 300, 0, 0, 1.0, 0.0, None, None, None) == -1
     assert L.clibd_softce_workspace_bytes(32, 32, 768) > 32 * 32 * 4
@@ -113,6 +113,51 @@ def test_layernorm_and_attention_argument_combinations_are_validated_on_the_host
     assert att_fwd(nq=32, lse=p, o_lo=p) == -1 and b"nq = out_seq = S" in L.clibd_last_error()
     assert att_fwd(out_fp8_scale=2.0, lse=p, o_lo=p) == -1 and b"bf16 out" in L.clibd_last_error()
     assert att_fwd(out_fp8_scale=-1.0) == -1 and b"fp8 scale" in L.clibd_last_error()
+
+
+def test_reduction_workspace_arguments_are_validated_on_the_host(lib):
+    """The workspace rule of the eight reductions that take their partials workspace as an argument (NULL, 0 = the atomic / plain form): a size
+    without a workspace, a short and a misaligned workspace are rejected before a launch, and the message names the size query."""
+    from clibd_amd import _lib
+
+    L = _lib.load()
+    p, odd = ctypes.c_void_p(256), ctypes.c_void_p(264)   # never dereferenced: every call below is rejected before a launch
+    big = 1 << 30
+    ep = _lib.GemmEpilogue()
+    ep.out_bf16, ep.ld_out_bf16 = 256, 768
+    # name -> (call(workspace, workspace_bytes), the size its query asks for); the TN products: the colsum workspace, with colsum_a given
+    entries = {
+        "gemm_bf16_nt": (lambda ws, n: L.clibd_gemm_bf16_nt(p, 3072, p, 3072, 50432, 768, 3072, ctypes.byref(ep), ws, n, None),
+                         L.clibd_gemm_tail_workspace_bytes(50432, 768, 3072)),
+        "transpose_colsum_bf16": (lambda ws, n: L.clibd_transpose_colsum_bf16(p, 768, 1000, 768, p, 1024, p, ws, n, None),
+                                  L.clibd_transpose_colsum_workspace_bytes(1024, 768)),
+        "colsum_bf16": (lambda ws, n: L.clibd_colsum_bf16(p, 768, 1000, 768, p, ws, n, None), L.clibd_colsum_workspace_bytes(1000, 768)),
+        "layernorm_param_grads": (lambda ws, n: L.clibd_layernorm_param_grads(p, 0, 768, p, p, 640, 768, p, p, 0, 0, 1.0, ws, n, None),
+                                  L.clibd_layernorm_param_grads_workspace_bytes(640, 768)),
+        "batch_sum_f32": (lambda ws, n: L.clibd_batch_sum_f32(p, 2048, 768, p, ws, n, None), L.clibd_batch_sum_workspace_bytes(2048, 768)),
+        "bert_embed_bwd": (lambda ws, n: L.clibd_bert_embed_bwd(p, None, p, 100, 768, 30522, 2, p, p, ws, n, None),
+                           L.clibd_bert_embed_bwd_workspace_bytes(100, 768, 30522, 2)),
+        "gemm_bf16_tn_splitk": (lambda ws, n: L.clibd_gemm_bf16_tn_splitk(p, 768, p, 768, 6272, 768, 768, p, 768, 1, p, p, big, ws, n, None),
+                                L.clibd_gemm_tn_colsum_workspace_bytes(6272, 768)),
+        "gemm_fp8b_tn_splitk": (lambda ws, n: L.clibd_gemm_fp8b_tn_splitk(p, 768, p, 768, 0.5, 6272, 768, 768, p, 768, 1, p, p, big, ws, n, None),
+                                L.clibd_gemm_tn_colsum_workspace_bytes(6272, 768)),
+    }
+    for name, (call, need) in entries.items():
+        assert need >= 32, name
+        assert call(None, 16) == -1 and b"workspace" in L.clibd_last_error(), name                    # a size without a workspace
+        assert call(p, need - 16) == -1, name                                                           # a short workspace
+        assert b"too small" in L.clibd_last_error() and b"_workspace_bytes" in L.clibd_last_error(), (name, L.clibd_last_error())
+        assert call(odd, big) == -1 and b"misaligned" in L.clibd_last_error(), name                    # 8-byte aligned only
+    # the TN products: a colsum workspace goes with colsum_a
+    need = L.clibd_gemm_tn_colsum_workspace_bytes(6272, 768)
+    assert L.clibd_gemm_bf16_tn_splitk(p, 768, p, 768, 6272, 768, 768, p, 768, 1, None, p, big, p, need, None) == -1
+    assert b"colsum_a" in L.clibd_last_error()
+    assert L.clibd_gemm_fp8b_tn_splitk(p, 768, p, 768, 0.5, 6272, 768, 768, p, 768, 1, None, p, big, p, need, None) == -1
+    assert b"colsum_a" in L.clibd_last_error()
+    # three token types: no fixed-order form, so rejected with a workspace; the atomic form takes them (H = 2048 is what stops this call)
+    assert L.clibd_bert_embed_bwd(p, p, p, 100, 768, 30522, 3, p, p, p, big, None) == -1 and b"token types" in L.clibd_last_error()
+    assert L.clibd_bert_embed_bwd(p, p, p, 100, 2048, 30522, 3, p, p, None, 0, None) == -1
+    assert b"token types" not in L.clibd_last_error() and b"H <= 1024" in L.clibd_last_error()
 
 
 def test_product_path_has_no_cpu_fallback():

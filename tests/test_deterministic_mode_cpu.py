@@ -9,9 +9,9 @@ import torch
 
 ROOT = Path(__file__).resolve().parents[1]
 NEW = ["clibd_layernorm_bwd_pg_workspace_bytes", "clibd_layernorm_bwd", "clibd_layernorm_param_grads_workspace_bytes",
-       "clibd_layernorm_param_grads_ordered", "clibd_batch_sum_workspace_bytes", "clibd_batch_sum_f32_ordered",
-       "clibd_bert_embed_bwd_workspace_bytes", "clibd_bert_embed_bwd_ordered", "clibd_colsum_workspace_bytes", "clibd_colsum_bf16_ordered",
-       "clibd_gemm_tn_colsum_workspace_bytes", "clibd_gemm_bf16_tn_splitk_ordered"]
+       "clibd_layernorm_param_grads", "clibd_batch_sum_workspace_bytes", "clibd_batch_sum_f32",
+       "clibd_bert_embed_bwd_workspace_bytes", "clibd_bert_embed_bwd", "clibd_colsum_workspace_bytes", "clibd_colsum_bf16",
+       "clibd_gemm_tn_colsum_workspace_bytes", "clibd_gemm_bf16_tn_splitk"]
 
 
 @pytest.fixture(scope="module")
@@ -29,7 +29,7 @@ def test_header_declares_and_library_exports_the_ordered_forms(L):
     declared = set(re.findall(r"\b(clibd_[a-z0-9_]+)\s*\(", text))
     for name in NEW:
         assert name in declared and name in _lib.SIGNATURES and hasattr(L, name), name
-    assert _lib.ABI_VERSION == 6 and L.clibd_abi_version() == 6
+    assert _lib.ABI_VERSION == 7 and L.clibd_abi_version() == 7
 
 
 def test_workspace_queries(L):
@@ -60,13 +60,14 @@ def test_host_side_validation_rejects_missing_or_short_workspaces(L):
     short = L.clibd_layernorm_bwd_pg_workspace_bytes(64, 768) - 16
     assert L.clibd_layernorm_bwd(p, None, p, p, p, 64, 768, None, None, None, None, p, 0, 0, 1.0, None, None, p, p, p, short, None) == -1
     assert b"too small" in L.clibd_last_error()
-    assert L.clibd_batch_sum_f32_ordered(p, 2048, 768, p, p, 16, None) == -1
-    assert L.clibd_colsum_bf16_ordered(p, 768, 1000, 768, p, None, 0, None) == -1
-    assert L.clibd_bert_embed_bwd_ordered(p, None, p, 100, 768, 30522, 2, p, p, p, 64, None) == -1
+    assert L.clibd_batch_sum_f32(p, 2048, 768, p, p, 16, None) == -1
+    # since ABI 7 a NULL workspace with size 0 selects the atomic form (it would launch): what stays rejected is a size without a workspace
+    assert L.clibd_colsum_bf16(p, 768, 1000, 768, p, None, 16, None) == -1
+    assert L.clibd_bert_embed_bwd(p, None, p, 100, 768, 30522, 2, p, p, p, 64, None) == -1
     assert b"too small" in L.clibd_last_error()
-    assert L.clibd_bert_embed_bwd_ordered(p, None, p, 100, 768, 30522, 3, p, p, p, 1 << 30, None) == -1   # three token types: no ordered form
-    assert L.clibd_layernorm_param_grads_ordered(p, 0, 768, p, p, 64, 768, p, p, 0, 0, 1.0, None, 0, None) == -1
-    assert L.clibd_gemm_bf16_tn_splitk_ordered(p, 768, p, 768, 6272, 768, 768, p, 768, 1, p, p, 1 << 30, p, 16, None) == -1
+    assert L.clibd_bert_embed_bwd(p, None, p, 100, 768, 30522, 3, p, p, p, 1 << 30, None) == -1   # three token types: no ordered form
+    assert L.clibd_layernorm_param_grads(p, 0, 768, p, p, 64, 768, p, p, 0, 0, 1.0, None, 16, None) == -1
+    assert L.clibd_gemm_bf16_tn_splitk(p, 768, p, 768, 6272, 768, 768, p, 768, 1, p, p, 1 << 30, p, 16, None) == -1
     assert b"colsum workspace" in L.clibd_last_error()
 
 

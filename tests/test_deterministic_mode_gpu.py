@@ -147,28 +147,28 @@ class _Recorder:
 
 def test_no_atomic_form_is_reached(dev, monkeypatch):
     """One deterministic full fine-tune step (8-bit dgrad on both towers, so that both LayerNorm parameter-gradient kernels run) and one
-    tri-modal LoRA step at B = 20: none of the atomic entry points is called."""
+    tri-modal LoRA step at B = 20: every reduction call carries its partials workspace (a NULL workspace selects the float atomics)."""
     from clibd_amd import _lib
     from clibd_amd.data import synthetic_batch
 
     real = _lib.load()
     rec = _Recorder(real)
     monkeypatch.setattr(_lib, "load", lambda: rec)
+    reductions = {"clibd_colsum_bf16", "clibd_batch_sum_f32", "clibd_bert_embed_bwd", "clibd_layernorm_param_grads", "clibd_transpose_colsum_bf16"}
     for model, batch in ((_full_model(dev).enable_fp8_dgrad("all").eval(), synthetic_batch(32, dev, seed=8, rank=0, with_text=False)),
                          (_lora_model(dev, text=True).eval(), synthetic_batch(20, dev, seed=8, rank=0, with_text=True))):
         rec.calls.clear()
         _step_grads(model, batch, True)
         names = [n for n, _ in rec.calls]
         assert "clibd_attention_bwd" in names, sorted(set(names))
-        banned = {"clibd_colsum_bf16", "clibd_batch_sum_f32", "clibd_bert_embed_bwd", "clibd_layernorm_param_grads", "clibd_transpose_colsum_bf16"}
-        hit = sorted({n for n in names if n in banned})
-        assert not hit, hit
         for n, a in rec.calls:
+            if n in reductions:   # (..., workspace, workspace_bytes, stream)
+                assert a[-3] is not None and a[-2] > 0, f"{n} without a partials workspace"
             if n == "clibd_layernorm_bwd" and a[17] is not None:   # dgamma
                 assert a[19] is not None and a[20] > 0, "LayerNorm parameter gradients without a workspace"
-            if n == "clibd_gemm_bf16_tn_splitk":
-                assert a[10] is None, "TN split-K with a bias column sum outside the ordered form"
-            if n in ("clibd_gemm_bf16_nt", "clibd_gemm_bf16_nt_ws"):
+            if n in ("clibd_gemm_bf16_tn_splitk", "clibd_gemm_fp8b_tn_splitk") and a[-6] is not None:   # colsum_a
+                assert a[-3] is not None and a[-2] > 0, "TN split-K with a bias column sum and no colsum workspace"
+            if n == "clibd_gemm_bf16_nt":
                 assert a[7]._obj.split_k <= 1, "generic split-K (atomic) weight gradient"
             if n in ("clibd_lora_backward", "clibd_lora_wgrad"):
                 assert a[-3] is not None and a[-2] > 0, "adapter gradients without a partials workspace"
@@ -295,3 +295,95 @@ def _lora_grads_f64(dqkv, x, t, dt, H):
     """float64 adapter gradients of the rank-(4+4) slot: dA_q = dt_q^T x, dA_v = dt_v^T x, dB_q = dq^T t_q, dB_v = dv^T t_v"""
     dq, dv, xd, td, dtd = dqkv[:, :H].double(), dqkv[:, 2 * H:].double(), x.double(), t.double(), dt.double()
     return [dtd[:, 0:4].t() @ xd, dtd[:, 4:8].t() @ xd, dq.t() @ td[:, 0:4], dv.t() @ td[:, 4:8]]
+
+
+# ---- the workspace forms at the smallest shapes that cross each cap of the partial count (where a wrong grid would overrun the workspace) ----
+def _ln_param_inputs(M, H):
+    g = torch.Generator(device="cpu").manual_seed(M + H)
+    x = torch.randn(M, H, generator=g) * 2 + 0.5
+    dy = torch.randn(M, H, generator=g)
+    mean = x.double().mean(1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(x.double().var(1, unbiased=False, keepdim=True) + 1e-12)
+    return x, dy, torch.cat([mean, rstd], dim=1).float()
+
+
+@pytest.mark.parametrize("M,H,f32dy,drop", [(65536 + 70, 64, False, False), (65536 + 70, 64, True, False), (70, 128, False, False), (70, 128, True, False),
+                                            (65536 + 70, 64, False, True)])
+def test_ordered_layernorm_param_grads(dev, M, H, f32dy, drop):
+    """(65536 + 70, 64): 1026 row chunks on the 1024 blocks of the workspace form, so two blocks make a second grid-stride sweep, the last chunk
+    ragged (6 rows); (70, 128): two blocks, the last ragged."""
+    from clibd_amd import ops
+    from oracle import clibd_oracle as O
+
+    x, dy, stats = _ln_param_inputs(M, H)
+    dyd = dy.to(dev) if f32dy else dy.to(dev, torch.bfloat16)
+    xd, std = x.to(dev), stats.to(dev)
+    d = ops.Drop(0.1, 99) if drop else None
+
+    def run():
+        dg, db = torch.zeros(H, device=dev), torch.zeros(H, device=dev)
+        ops.layernorm_param_grads(dyd, xd, std, dg, db, drop=d, ordered=True)
+        return torch.cat([dg, db])
+
+    out = _three(run)
+    dyr = dyd.double().cpu()
+    if drop:
+        idx = torch.arange(M, dtype=torch.int64)[:, None] * H + torch.arange(H, dtype=torch.int64)[None, :]
+        dyr = dyr * O.drop_factor(99, idx, 0.1).double()
+    xhat = (x.double() - stats[:, :1].double()) * stats[:, 1:].double()
+    _close(out[:H], (dyr * xhat).sum(0))
+    _close(out[H:], dyr.sum(0))
+
+
+def _colsum_input():
+    return torch.randn(65536 + 257, 64, generator=torch.Generator(device="cpu").manual_seed(5)).to(torch.bfloat16)
+
+
+def test_ordered_colsum_beyond_the_row_cap(dev):
+    """65 793 rows: 258 chunks of 256 rows on the 256 partial rows of the workspace form (a second sweep, the last chunk one row)."""
+    from clibd_amd import ops
+
+    y = _colsum_input().to(dev)
+    _close(_three(lambda: (lambda o: (ops.colsum_bf16(y, o, ordered=True), o)[1])(torch.zeros(64, device=dev))), y.double().sum(0))
+
+
+def _batch_sum_input(B):
+    return torch.randn(B, 300, generator=torch.Generator(device="cpu").manual_seed(B))
+
+
+@pytest.mark.parametrize("B", [63, 64, 70])
+def test_ordered_batch_sum_chunking(dev, B):
+    """B = 63: one chunk; 64: eight chunks of 8 rows; 70: eight chunks of 9 rows, the last holding 7."""
+    from clibd_amd import ops
+
+    x = _batch_sum_input(B).to(dev)
+    _close(_three(lambda: (lambda o: (ops.batch_sum(x, o, ordered=True), o)[1])(torch.zeros(300, device=dev))), x.double().sum(0))
+
+
+def _tn_inputs(M, Na, Nb, fp8):
+    g = torch.Generator(device="cpu").manual_seed(M + Na + (1 if fp8 else 0))
+    a = (0.1 * torch.randn(M, Na, generator=g)).to(torch.bfloat16)
+    b = torch.randn(M, Nb, generator=g)
+    return a, (b.to(torch.float8_e4m3fn) if fp8 else (0.1 * b).to(torch.bfloat16))
+
+
+@pytest.mark.parametrize("fp8", [False, True])
+@pytest.mark.parametrize("M", [256, 1024])
+def test_ordered_tn_splitk_colsum_slices(dev, M, fp8):
+    """One output tile (Na = Nb = 256).  M = 256: one slice; M = 1024: several slices of that tile, the column sums one partial per slice."""
+    from clibd_amd import ops
+
+    Na = Nb = 256
+    a, b = _tn_inputs(M, Na, Nb, fp8)
+    ad, bd = a.to(dev), b.to(dev)
+    scale = dict(b_scale=0.5) if fp8 else {}
+
+    def tn():
+        out, cs = torch.zeros((Na, Nb), device=dev), torch.zeros(Na, device=dev)
+        assert ops.gemm_tn_splitk(ad, bd, out, accumulate=True, colsum=cs, ordered=True, **scale)
+        return torch.cat([out.view(-1), cs])
+
+    got = _three(tn)
+    bref = b.float().double() * (0.5 if fp8 else 1.0)
+    _close(got[Na * Nb:], a.double().sum(0))
+    _close(got[:Na * Nb], (a.double().t() @ bref).view(-1), tol=1e-4)

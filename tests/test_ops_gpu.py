@@ -1397,7 +1397,7 @@ def test_key_bank_cache_follows_the_callers_tensor(dev):
 @pytest.mark.parametrize("M,N,K,parts,tail", [(50432, 768, 3072, 3, 79), (50432, 768, 2304, 3, 79), (43776, 768, 3072, 4, 1), (50400, 768, 3072, 3, 79),
                                               (22528, 768, 1536, 4, 8)])
 def test_gemm_stream_k_tail_is_exact_and_deterministic(ops, dev, M, N, K, parts, tail):
-    """clibd_gemm_bf16_nt_ws: the last, partial tile round cut into K-slices over the idle CUs (per-rank shapes of the 8-GPU configuration: 591 tiles =
+    """clibd_gemm_bf16_nt with its tail workspace: the last, partial tile round cut into K-slices over the idle CUs (per-rank shapes of the 8-GPU configuration: 591 tiles =
     2 full rounds + 79 tiles -> 3 slices each).  Integer operands make every product and partial sum exact in fp32, so every epilogue kind that has the
     form must equal the plain launch BIT FOR BIT (and the fp64 statement where there is one): plain bf16 output, + adapters' rank update, + bf16 aux,
     bias + fp32 residual, bias -> dropout -> + fp32 residual; ragged M; the flags are back at zero; two runs give the same bits."""

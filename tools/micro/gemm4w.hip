@@ -307,7 +307,7 @@ struct Board {   // sysfs hwmon of THIS process's device (matched by PCI bus id)
     double mhz() const { return dir.empty() ? -1 : rd(dir + "/freq1_input") / 1e6; }
 };
 
-typedef int (*gemm_fn)(const void*, int, const void*, int, int, int, int, const clibd_gemm_epilogue*, void*);
+typedef int (*gemm_fn)(const void*, int, const void*, int, int, int, int, const clibd_gemm_epilogue*, void*, size_t, void*);
 
 int main(int argc, char** argv) {
     if (argc < 2) { fprintf(stderr, "usage: %s <libclibd_hip.so> [seconds per arm]\n", argv[0]); return 2; }
@@ -343,7 +343,7 @@ int main(int argc, char** argv) {
         memset(&ep, 0, sizeof(ep));
         ep.split_k = 1; ep.ld_out_bf16 = N;
         auto run = [&](int arm) {
-            if (arm == 0) { ep.out_bf16 = dO[0]; if (ref(dA, K, dW, K, M, N, K, &ep, st) != 0) { fprintf(stderr, "reference gemm failed\n"); exit(1); } }
+            if (arm == 0) { ep.out_bf16 = dO[0]; if (ref(dA, K, dW, K, M, N, K, &ep, nullptr, 0, st) != 0) { fprintf(stderr, "reference gemm failed\n"); exit(1); } }
             else if (arm == 1) { p.out = dO[1]; hipLaunchKernelGGL(gemm4w_kernel<false>, dim3(ncu), dim3(256), LDS_BYTES, st, p); }
             else { p.out = dO[2]; hipLaunchKernelGGL(gemm4w_kernel<true>, dim3(ncu), dim3(256), LDS_BYTES, st, p); }
         };

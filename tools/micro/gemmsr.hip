@@ -553,7 +553,7 @@ struct Board {   // sysfs hwmon of THIS process's device (matched by PCI bus id)
     double mhz() const { return dir.empty() ? -1 : rd(dir + "/freq1_input") / 1e6; }
 };
 
-typedef int (*gemm_fn)(const void*, int, const void*, int, int, int, int, const clibd_gemm_epilogue*, void*);
+typedef int (*gemm_fn)(const void*, int, const void*, int, int, int, int, const clibd_gemm_epilogue*, void*, size_t, void*);
 
 typedef void (*kern_t)(PS, long long*);
 struct Arm { const char* name; kern_t fn; int lds; };
@@ -618,7 +618,7 @@ int main(int argc, char** argv) {
         CK(hipMalloc(&dstamps, (size_t)ncu * 16 * 2 * 4 * sizeof(long long)));
         auto run = [&](int arm) {
             long long* nul = nullptr;
-            if (arm == 0) { ep.out_bf16 = dRef; if (ref(dA, K, dW, K, M, N, K, &ep, st) != 0) { fprintf(stderr, "reference gemm failed\n"); exit(1); } }
+            if (arm == 0) { ep.out_bf16 = dRef; if (ref(dA, K, dW, K, M, N, K, &ep, nullptr, 0, st) != 0) { fprintf(stderr, "reference gemm failed\n"); exit(1); } }
             else hipLaunchKernelGGL(arms[arm].fn, dim3(ncu), dim3(512), arms[arm].lds, st, p, nul);
         };
         // ---- correctness: the product kernel against a host fp64 dot product on sampled entries, every arm against the product kernel on everything
