@@ -111,7 +111,10 @@ __device__ __forceinline__ void store_rows16_lo(unsigned short* row_lo, const f3
     store_rows16(row_lo, lo, 1.0f, on, g);
 }
 
-constexpr float NEG_BIG = -1.0e30f;
+// A power of two: NEG_BIG * c2 is then exact in fp32, so a row whose keys are ALL masked has fma(NEG_BIG, c2, -(NEG_BIG * c2)) = 0 and
+// every probability exp2(0) = 1 (uniform weight, finite results).  With -1.0e30f the product rounds, the fused multiply-add returns the
+// rounding error (8e20), exp2 of it is +inf and the row leaves as NaN.  For every other row nothing changes: a masked score still underflows to 0.
+constexpr float NEG_BIG = -0x1p100f;
 
 #ifdef CLIBD_GEMM_DIAG
 // diagnostic build only (python -m clibd_amd.build --diag; tools/att_stamps.py): s_memtime at the phase boundaries of the backward
@@ -130,6 +133,48 @@ __device__ long long* g_att_stamps = nullptr;   // [workgroup][8]
 #define ATT_STAMP(k) do { } while (0)
 #define SP_STAMP(k) do { } while (0)
 #endif
+
+// The key-padding mask, branch-free on purpose.  The short-circuit form (`key < S && key_mask[...] != 0`, evaluated per score) became one branch
+// per key, and in the forms of ten and more key tiles the compiler dropped the select of key tile 0, register 0 from its branch: keys 0, 4, 8
+// and 12 were never masked (a prefix mask, all that the towers and the older tests send, never masks those; tests/test_attention_forms_gpu.py
+// sends masks with holes).  The address is clamped, so every mask word can be loaded unconditionally and combined with a plain AND.
+template <bool MASK>
+__device__ __forceinline__ bool key_live(const int* __restrict__ key_mask, int b, int S, int key) {
+    if constexpr (MASK) {
+        const int m = key_mask[(size_t)b * S + min(key, S - 1)];
+        return (key < S) & (m != 0);
+    } else {
+        return key < S;
+    }
+}
+// The two words are all that may stay alive of the mask: an empty asm that "rewrites" them keeps the compiler from carrying the sixteen shifted
+// ballot words (or, hoisted out of the query loop, one blend mask per score) in registers instead, which cost the masked long forms scratch.
+__device__ __forceinline__ void pin_live(unsigned (&live)[2]) { asm volatile("" : "+v"(live[0]), "+v"(live[1])); }
+// The keys a lane holds scores for are the same for every query tile of a head: key 16 kt + 4 g + r in register (kt, r).  Their mask is read ONCE per
+// head (instead of once per query tile and score): the wave loads 64 consecutive mask words per step, one per lane, a ballot turns them into a
+// wave-uniform word, and each lane picks the four bits of its keys of every tile into bit 4 kt + r of live[].  Every lane of the wave must call this.
+template <int NKT>
+__device__ __forceinline__ void live_key_bits(const int* __restrict__ key_mask, int b, int S, int lane, unsigned (&live)[2]) {
+    const int g = lane >> 4;
+    live[0] = 0u; live[1] = 0u;
+#pragma unroll
+    for (int j = 0; j < (NKT + 3) / 4; ++j) {
+        const unsigned long long w = __builtin_amdgcn_ballot_w64(key_live<true>(key_mask, b, S, 64 * j + lane));   // bit L: key 64 j + L passes
+#pragma unroll
+        for (int kq = 0; kq < 4; ++kq) {
+            const int kt = 4 * j + kq;
+            if (kt < NKT) live[(4 * kt) >> 5] |= ((unsigned)(w >> (16 * kq + 4 * g)) & 0xFu) << ((4 * kt) & 31);
+        }
+    }
+    pin_live(live);
+}
+
+// score, or NEG_BIG where bit `bit` of live[] is clear: a bit-field extract and a bitwise blend — no compare, so no lane-mask register per score
+// (forty to sixty-four of them, hoisted out of the query loop, cost the masked forms their scalar registers and then scratch)
+__device__ __forceinline__ float masked_score(float sc, const unsigned (&live)[2], int bit) {
+    const unsigned keep = (unsigned)(((int)(live[bit >> 5] << (31 - (bit & 31)))) >> 31);   // all ones if the key passes
+    return __uint_as_float((__float_as_uint(sc) & keep) | (__float_as_uint(NEG_BIG) & ~keep));
+}
 
 // ============================================ forward ==========================================================
 // MASK: a key-padding mask is present (text tower).  Compile-time, because the per-key mask loads and their divergent
@@ -168,6 +213,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
     // NKT is even (k-slots of 32 keys); when S <= 16 (NKT - 1) the last key tile is all padding (S = 197 -> 13 live tiles of
     // 14, S = 133 -> 9 of 10): its score MFMAs and exponentials are skipped (probabilities exactly 0, as the mask gives)
     const bool last_live = (IMG == S_pad) && S > 16 * (NKT - 1);   // (a short image is only launched with S <= 16 (NKT - 1): compile-time false)
+    unsigned live[2] = {~0u, ~0u};   // MASK: which of this lane's keys pass (live_key_bits); the loads ride along with the staging
+    if constexpr (MASK) live_key_bits<NKT>(key_mask, b, S, lane, live);
     // this wave's first Q fragment rides along with the K/V staging; later ones are prefetched a tile ahead
     bf16x8 qf[2];
     {
@@ -187,6 +234,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
         // Two query tiles per wave and sweep: every K row fragment and every transposed V fragment read from LDS feeds two
         // MFMAs (the one-tile sweep moves 1 KiB of LDS per MFMA and is bound by it).  Arithmetic per element is unchanged.
         for (int p = wave; p < ((nqt + 1) >> 1); p += NW) {
+            if constexpr (MASK) pin_live(live);
             bf16x8 qf2[2][2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
@@ -206,6 +254,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
                         sc[0][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, qf2[0][ks], sc[0][kt], 0, 0, 0);
                         sc[1][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, qf2[1][ks], sc[1][kt], 0, 0, 0);
                     }
+                    if constexpr (MASK) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { sc[0][kt][r] = masked_score(sc[0][kt][r], live, 4 * kt + r); sc[1][kt][r] = masked_score(sc[1][kt][r], live, 4 * kt + r); }
+                    }
                 }
                 if (kt & 1) __builtin_amdgcn_sched_barrier(0);  // at most four K fragments in flight: 2 x NKT score quads leave no room for more
             }
@@ -216,12 +268,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
 #pragma unroll
                 for (int kt = 0; kt < NKT; ++kt) {
                     if (kt == NKT - 1 && !last_live) continue;
-                    if (MASK || (kt >= NKT - 2 && kt * 16 + 15 >= S)) {   // S > 16 (NKT - 2): only the last two tiles can hold padding keys
+                    if (!MASK && kt >= NKT - 2 && kt * 16 + 15 >= S) {   // S > 16 (NKT - 2): only the last two tiles can hold padding keys (MASK: done above, with the mask)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int key = kt * 16 + 4 * g + r;
                             bool ok = key < S;
-                            if (MASK) ok = ok && key_mask[(size_t)b * S + min(key, S - 1)] != 0;
                             if (!ok) sc[t][kt][r] = NEG_BIG;
                         }
                     }
@@ -300,6 +351,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
     }
     for (int qt = wave; qt < nqt; qt += NW) {
         const int q = qt * 16 + i;
+        if constexpr (MASK) pin_live(live);
         f32x4 sc[NKT];
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
@@ -308,6 +360,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
                 sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row_frag(kt_lds, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
+            if constexpr (MASK) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sc[kt][r] = masked_score(sc[kt][r], live, 4 * kt + r);
+            }
         }
         {   // prefetch the next tile's Q fragment (clamped; unused after the last tile)
             const int qn = min((qt + NW) * 16 + i, S - 1);
@@ -318,12 +374,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
             if (kt == NKT - 1 && !last_live) continue;
-            if (MASK || (kt >= NKT - 2 && kt * 16 + 15 >= S)) {  // only tiles that can hold masked keys pay for the test
+            if (!MASK && kt >= NKT - 2 && kt * 16 + 15 >= S) {  // only tiles that can hold masked keys pay for the test
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int key = kt * 16 + 4 * g + r;
                     bool ok = key < S;
-                    if (MASK) ok = ok && key_mask[(size_t)b * S + min(key, S - 1)] != 0;
                     if (!ok) sc[kt][r] = NEG_BIG;
                 }
             }
@@ -458,6 +513,8 @@ __global__ __launch_bounds__(64 * ATTP_WAVES) void attention_fwd_persistent_kern
         }
         stored = mine;
         if (mine) {
+            unsigned live[2] = {~0u, ~0u};
+            if constexpr (MASK) live_key_bits<NKT>(key_mask, b, S, lane, live);
             f32x4 sc[NKT];
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt) {
@@ -466,17 +523,20 @@ __global__ __launch_bounds__(64 * ATTP_WAVES) void attention_fwd_persistent_kern
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
                     sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row_frag(kt_lds, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
+                if constexpr (MASK) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sc[kt][r] = masked_score(sc[kt][r], live, 4 * kt + r);
+                }
             }
             float mx = NEG_BIG;
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt) {
                 if (kt == NKT - 1 && !last_live) continue;
-                if (MASK || (kt >= NKT - 2 && kt * 16 + 15 >= S)) {  // only tiles that can hold masked keys pay for the test
+                if (!MASK && kt >= NKT - 2 && kt * 16 + 15 >= S) {  // only tiles that can hold masked keys pay for the test
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int key = kt * 16 + 4 * g + r;
                         bool ok = key < S;
-                        if (MASK) ok = ok && key_mask[(size_t)b * S + min(key, S - 1)] != 0;
                         if (!ok) sc[kt][r] = NEG_BIG;
                     }
                 }
@@ -560,11 +620,13 @@ __global__ __launch_bounds__(64 * ATTP_WAVES) void attention_fwd_persistent_kern
 #ifndef CLIBD_ATT_BWD_S160_WAVES
 #define CLIBD_ATT_BWD_S160_WAVES 3
 #endif
-constexpr int att_bwd_min_waves(int NKT, bool MASK, int NW) {
-    return NKT > 10 ? CLIBD_ATT_BWD_LONG_WAVES : (NKT == 10 && NW == 4 && !MASK) ? CLIBD_ATT_BWD_S160_WAVES : 3;
+constexpr int att_bwd_min_waves(int NKT, bool MASK, int NW, bool DROP) {
+    // (the masked four-wave ten-tile form, S in (128, 160] with a key mask, needs 20 bytes of scratch at the three-wave cap: two waves, no scratch)
+    // (sixteen tiles with a mask AND dropout need 12 bytes at two waves: one wave per SIMD)
+    return NKT > 10 ? ((NKT == 16 && MASK && DROP) ? 1 : CLIBD_ATT_BWD_LONG_WAVES) : (NKT == 10 && NW == 4) ? (MASK ? 2 : CLIBD_ATT_BWD_S160_WAVES) : 3;
 }
 template <int NKT, bool PAIR, bool MASK, bool DROP, int NW = ATT_WAVES, int IMG = 16 * NKT>
-__global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW)) void attention_bwd_kernel(const unsigned short* __restrict__ qkv,
+__global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) void attention_bwd_kernel(const unsigned short* __restrict__ qkv,
                                                                     const unsigned short* __restrict__ dout, int S,
                                                                     int nheads, const int* __restrict__ key_mask,
                                                                     unsigned short* __restrict__ dqkv, float scale,
@@ -591,6 +653,8 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW)) void att
     const int g = lane >> 4, i = lane & 15;
 
     const float c2 = scale * 1.4426950408889634f;
+    unsigned live[2] = {~0u, ~0u};
+    if constexpr (MASK) live_key_bits<NKT>(key_mask, b, S, lane, live);
     bf16x8 qf[2], dof[2];
     {
         const int qc0 = min(wave * 16 + i, S - 1);
@@ -628,6 +692,7 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW)) void att
     }
     for (int qt = wave; qt < nqt; qt += NW) {
         const int q = qt * 16 + i;
+        if constexpr (MASK) pin_live(live);
         if (q >= nq) {  // rows of an active tile beyond nq: their dO is zero
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) dof[ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
@@ -642,6 +707,10 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW)) void att
             for (int ks = 0; ks < 2; ++ks) {
                 sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row_frag(t0, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
                 dp[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row_frag(t1, kt * 16 + i, ks, g), dof[ks], dp[kt], 0, 0, 0);
+            }
+            if constexpr (MASK) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sc[kt][r] = masked_score(sc[kt][r], live, 4 * kt + r);
             }
         }
         if (DROP) {  // O = (P o M / (1-p)) V  =>  dP = (dO V^T) o M / (1-p)
@@ -667,12 +736,11 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW)) void att
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
             if (kt == NKT - 1 && !last_live) continue;
-            if (MASK || (kt >= NKT - 2 && kt * 16 + 15 >= S)) {  // only tiles that can hold masked keys pay for the test
+            if (!MASK && kt >= NKT - 2 && kt * 16 + 15 >= S) {  // only tiles that can hold masked keys pay for the test
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int key = kt * 16 + 4 * g + r;
                     bool ok = key < S;
-                    if (MASK) ok = ok && key_mask[(size_t)b * S + min(key, S - 1)] != 0;
                     if (!ok) sc[kt][r] = NEG_BIG;
                 }
             }
@@ -768,9 +836,7 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW)) void att
         for (int j = 0; j < 2; ++j) {
             const int key = (2 * p + j) * 16 + i;
             keyv[j] = key;
-            bool ok = key < S;
-            if (MASK) ok = ok && key_mask[(size_t)b * S + min(key, S - 1)] != 0;
-            key_ok[j] = ok;
+            key_ok[j] = key_live<MASK>(key_mask, b, S, key);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) { kf[j][ks] = kfs[pi][j][ks]; vf[j][ks] = vfs[pi][j][ks]; }
         }
@@ -887,8 +953,7 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW)) void att
     const int nkt = (S + 15) >> 4;
     for (int kt = wave; kt < nkt; kt += NW) {
         const int key = kt * 16 + i;
-        bool key_ok = key < S;
-        if (MASK) key_ok = key_ok && key_mask[(size_t)b * S + min(key, S - 1)] != 0;
+        const bool key_ok = key_live<MASK>(key_mask, b, S, key);
         {   // next key tile's K / V fragments fly during this tile's sweep over the queries
 #ifdef CLIBD_ATT_NO_REFETCH
             const int kn = min((kt + NW) * 16 + i, IMG - 1);
@@ -1098,7 +1163,7 @@ __global__ __launch_bounds__(64 * ATTB_WAVES) void attention_bwd_sp_kernel(const
                     pf[j] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
                     dsf[j] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
                     if (j >= nown) continue;
-                    const bool key_live = keyv[j] < S;   // padding keys of the last live tile: no probability, no dS (dQ sums over keys)
+                    const bool klive = keyv[j] < S;   // padding keys of the last live tile: no probability, no dS (dQ sums over keys)
                     f32x4 pp[2], dd[2];
 #pragma unroll
                     for (int hq = 0; hq < 2; ++hq) {
@@ -1114,7 +1179,7 @@ __global__ __launch_bounds__(64 * ATTB_WAVES) void attention_bwd_sp_kernel(const
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             float pr = __builtin_amdgcn_exp2f(fmaf(sv[r], c2, -mr[hq][r]));   // normalised; 0 for query rows >= S
-                            if (!key_live) pr = 0.f;
+                            if (!klive) pr = 0.f;
                             float fm = 1.0f;
                             if (DROP) {
                                 const int qq = (2 * s + hq) * 16 + 4 * g + r;
@@ -1256,13 +1321,19 @@ extern "C" int clibd_attention_fwd(const void* qkv, int B, int S, int nheads, co
     do {                                                                                                          \
         /* The dropout forms of the persistent kernel that spill 2-10 registers at its 128-register cap (dropout with a key mask, dropout at sixteen tiles) were measured   */ \
         /* against the spill-free per-head kernel in round 6 (knob = 0): 207 / 242 us persistent against 265-269 / 299 us per head at S = 220 / 250: the persistent forms stay */ \
-        constexpr bool PERSIST_OK = CLIBD_ATT_FWD_PERSISTENT_SPILLING || !(DRP && (MSK || N >= 16));               \
-        if (PERSIST_OK && N >= 12 && total >= 2 * num_cus) {   /* S > 160: at S = 133 only 9 of the 16 waves have a tile and the per-head kernel wins */ \
-            constexpr int NP = (PERSIST_OK && N >= 12) ? N : 12;   /* (only the long-sequence, spill-free forms are instantiated) */             \
-            hipFuncSetAttribute((const void*)attention_fwd_persistent_kernel<NP, MSK, DRP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp); \
-            hipLaunchKernelGGL((attention_fwd_persistent_kernel<NP, MSK, DRP>), dim3(num_cus), dim3(64 * ATTP_WAVES), ldsp, st, \
-                               (const unsigned short*)qkv, S, nheads, total, (const int*)key_mask, (unsigned short*)out, scale, nq, out_seq, \
-                               drop_seed, drop_thr16, drop_scale, out_fp8_scale, lse, (unsigned short*)o_lo);      \
+        /* Two masked forms would need 12-20 bytes of scratch at that cap and have no such measurement: they take the spill-free per-head kernel */ \
+        constexpr bool PERSIST_OK = (CLIBD_ATT_FWD_PERSISTENT_SPILLING || !(DRP && (MSK || N >= 16))) && !(MSK && ((N == 12 && DRP) || (N == 14 && !DRP))); \
+        bool persistent = false;                                                                                  \
+        if constexpr (PERSIST_OK && N >= 12) {   /* S > 160: at S = 133 only 9 of the 16 waves have a tile and the per-head kernel wins; only these forms are instantiated */ \
+            if (total >= 2 * num_cus) {                                                                           \
+                persistent = true;                                                                                \
+                hipFuncSetAttribute((const void*)attention_fwd_persistent_kernel<N, MSK, DRP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp); \
+                hipLaunchKernelGGL((attention_fwd_persistent_kernel<N, MSK, DRP>), dim3(num_cus), dim3(64 * ATTP_WAVES), ldsp, st, \
+                                   (const unsigned short*)qkv, S, nheads, total, (const int*)key_mask, (unsigned short*)out, scale, nq, out_seq, \
+                                   drop_seed, drop_thr16, drop_scale, out_fp8_scale, lse, (unsigned short*)o_lo);  \
+            }                                                                                                     \
+        }                                                                                                         \
+        if (persistent) {                                                                                         \
         } else if (N == 10 && S <= 144 && S > 128 && nq > 128 && three_waves) {   /* nine query tiles: 3 + 3 + 3 on three waves */ \
             hipFuncSetAttribute((const void*)attention_fwd_kernel<10, false, MSK, DRP, 3, 144>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3); \
             hipLaunchKernelGGL((attention_fwd_kernel<10, false, MSK, DRP, 3, 144>), dim3(B * nheads), dim3(192), lds3, st,   \

@@ -233,7 +233,8 @@ int clibd_layernorm_bwd(const void* dy_bf16, const float* dy_f32, const float* x
  * BERT-small 20).  qkv bf16 [B*S, 3*H] packed [q | k | v] per row (timm Attention.forward layout
  * image_encoder.py:20-24; HF BertSelfAttention with q/k/v weights concatenated).
  * key_mask (optional) int32 [B,S], 1 = attend, 0 = masked (HF extended attention mask,
- * language_encoder.py:89 via BertModel).  out bf16 [B*S, H].
+ * language_encoder.py:89 via BertModel).  out bf16 [B*S, H].  A sequence whose keys are ALL masked has no defined softmax: its
+ * outputs and gradients are finite but otherwise unspecified (uniform weight over the padded key image), and no caller sends one.
  * Query prefix: only query rows [0, nq) of every sequence are evaluated (nq = S: everything; nq = 1: the [CLS]-only
  * attention of the last ViT block, whose other outputs the reference computes and discards, image_encoder.py:107 ->
  * timm pools token 0).  out / dout hold `out_seq` (>= nq) rows per sequence: row (b*out_seq + q).  The backward writes
