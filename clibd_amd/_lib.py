@@ -132,6 +132,14 @@ SIGNATURES = {
     "clibd_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
 }
 
+# the SimCLR entries (include/clibd_hip_simclr.h): a second, purely additive table bound after the first; the ABI version does not move
+EXT_SIGNATURES = {
+    "clibd_ntxent_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_ntxent_fwd": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_ntxent_bwd": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_adam_l2_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -155,7 +163,7 @@ def load() -> C.CDLL:
             "clibd_amd has no CPU fallback for its compute path."
         )
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -21,7 +21,7 @@ INCLUDE = HERE.parent / "include"
 LIB = HERE / "libclibd_hip.so"
 OBJ = CSRC / "build"
 ARCH = "gfx950"
-SOURCES = ["capi", "gemm", "gemm256", "gemm256_tn", "layernorm", "attention", "lora", "elementwise", "loss", "topk", "paramgrad", "evalacc", "augment"]
+SOURCES = ["capi", "gemm", "gemm256", "gemm256_tn", "layernorm", "attention", "lora", "elementwise", "loss", "topk", "paramgrad", "evalacc", "augment", "ntxent"]
 
 
 def csrc_hash() -> str:
@@ -29,7 +29,7 @@ def csrc_hash() -> str:
     import hashlib
 
     h = hashlib.sha256()
-    for f in sorted(list(CSRC.glob("*.hip")) + list(CSRC.glob("*.h")) + [INCLUDE / "clibd_hip.h"]):
+    for f in sorted(list(CSRC.glob("*.hip")) + list(CSRC.glob("*.h")) + [INCLUDE / "clibd_hip.h", INCLUDE / "clibd_hip_simclr.h"]):
         h.update(f.name.encode())
         h.update(f.read_bytes())
     return h.hexdigest()[:16]
@@ -43,7 +43,7 @@ def _hipcc() -> str:
 
 
 def _deps() -> list[Path]:
-    return [p for p in CSRC.glob("*.h")] + [INCLUDE / "clibd_hip.h"]
+    return [p for p in CSRC.glob("*.h")] + [INCLUDE / "clibd_hip.h", INCLUDE / "clibd_hip_simclr.h"]
 
 
 def _stale(target: Path, srcs: list[Path]) -> bool:

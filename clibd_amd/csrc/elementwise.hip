@@ -1,6 +1,7 @@
 // HBM/latency-bound helpers of the CLIBD step: embeddings, head tails, L2 normalisation, reductions, AdamW.
 #include "common.h"
 #include "../../include/clibd_hip.h"
+#include "../../include/clibd_hip_simclr.h"
 #include "host_util.h"
 
 namespace clibd {
@@ -409,6 +410,23 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
 }
 
+// ---- fused Adam with coupled L2 on a flat bucket (torch.optim.Adam(weight_decay=wd): the decay joins the gradient BEFORE the moments) ----
+__global__ __launch_bounds__(256) void adam_l2_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                      float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
+                                                      float beta1, float beta2, float eps, float wd, float bc1,
+                                                      float bc2_sqrt, float grad_scale) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float pi = p[i];
+        const float gi = g[i] * grad_scale + wd * pi;
+        const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
+        const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        p[i] = pi - (lr / bc1) * (mi / denom);
+    }
+}
+
 
 }  // namespace clibd
 
@@ -649,4 +667,16 @@ extern "C" int clibd_adamw_step(float* p, const float* g, float* m, float* v, si
     hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
                        weight_decay, bc1, sqrtf(bc2), grad_scale);
     return check_launch("adamw");
+}
+
+extern "C" int clibd_adam_l2_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, int step, float grad_scale, void* stream) {
+    if (!p || !g || !m || !v) return set_error(CLIBD_EINVAL, "adam_l2: null pointer");
+    if (step < 1) return set_error(CLIBD_EINVAL, "adam_l2: step must be >= 1");
+    if (n == 0) return CLIBD_OK;
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2 = 1.0f - powf(beta2, (float)step);
+    hipLaunchKernelGGL(adam_l2_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
+                       weight_decay, bc1, sqrtf(bc2), grad_scale);
+    return check_launch("adam_l2");
 }

@@ -1019,6 +1019,13 @@ def dense_head_backward(dout_f32: torch.Tensor, x_bf16: torch.Tensor, weight: to
     if not fused_bias:
         ops.colsum_bf16(dy_b, grads[id(bias)], **_ordered(ordered))
     w_t = ops.cast_transpose_bf16(_f32c(weight))   # [K, D]
+    if D % 64 != 0:
+        # a head width that is no multiple of the GEMM's K tile (timm's 1000-class head under SimCLR): zero-pad the contraction
+        Dp = (D + 63) // 64 * 64
+        dy_p, w_p = dy_b.new_zeros((M, Dp)), w_t.new_zeros((K, Dp))
+        dy_p[:, :D].copy_(dy_b)
+        w_p[:, :D].copy_(w_t)
+        dy_b, w_t = dy_p, w_p
     if out_bf16:
         dx = torch.empty((M, K), dtype=BF16, device=dy_b.device)
         ops.gemm_nt(dy_b, w_t, out_bf16=dx)

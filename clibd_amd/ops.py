@@ -804,6 +804,49 @@ def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale
                                        float(eps), float(weight_decay), int(step), float(grad_scale), _stream()), "adamw_step")
 
 
+def adam_l2_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0) -> None:
+    """torch.optim.Adam(weight_decay=...) on a flat bucket: the decay is L2 added to the gradient (include/clibd_hip_simclr.h)."""
+    for nm, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        _chk(t, F32, nm)
+    n = p.numel()
+    if g.numel() != n or m.numel() != n or v.numel() != n:
+        raise ValueError("adam_l2_step: size mismatch")
+    check(_lib.load().clibd_adam_l2_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, float(lr), float(beta1), float(beta2),
+                                         float(eps), float(weight_decay), int(step), float(grad_scale), _stream()), "adam_l2_step")
+
+
+def ntxent_workspace(N: int, D: int, device) -> torch.Tensor:
+    nbytes = _lib.load().clibd_ntxent_workspace_bytes(N, D)
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
+def ntxent_fwd(f: torch.Tensor, inv_temperature: float, loss: torch.Tensor, ws: torch.Tensor, top1: Optional[torch.Tensor] = None) -> None:
+    """NT-Xent over the [2b, D] raw features `f` (rows i and i + b are the two views of sample i): `loss` and `top1` are 1-element
+    device tensors that are overwritten; `ws` (ntxent_workspace) carries the row statistics to ntxent_bwd."""
+    _chk(f, F32, "f")
+    _chk(loss, F32, "loss")
+    if top1 is not None:
+        _chk(top1, I32, "top1")
+    if f.dim() != 2:
+        raise ValueError("ntxent_fwd: expected [2b, D] features")
+    N, D = f.shape
+    check(_lib.load().clibd_ntxent_fwd(f.data_ptr(), N, D, float(inv_temperature), loss.data_ptr(), _p(top1), ws.data_ptr(), ws.numel(),
+                                       _stream()), "ntxent_fwd")
+
+
+def ntxent_bwd(f: torch.Tensor, inv_temperature: float, df: torch.Tensor, ws: torch.Tensor, dloss: Optional[torch.Tensor] = None) -> None:
+    """d loss / d f into `df` (overwritten), times the device scalar `dloss` when given; must follow ntxent_fwd on the same `ws`."""
+    _chk(f, F32, "f")
+    _chk(df, F32, "df")
+    if dloss is not None:
+        _chk(dloss, F32, "dloss")
+    if f.dim() != 2 or df.shape != f.shape:
+        raise ValueError("ntxent_bwd: shapes")
+    N, D = f.shape
+    check(_lib.load().clibd_ntxent_bwd(f.data_ptr(), N, D, float(inv_temperature), _p(dloss), df.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _stream()), "ntxent_bwd")
+
+
 def topk_ip(q: torch.Tensor, keys: torch.Tensor, k: int = 5):
     """Exact fp32 inner-product top-k (faiss.IndexFlatIP.search): returns (similarities fp32 [Q,k], indices int64 [Q,k]).
     Streaming: scores never leave the MFMA accumulators' running top-8 lists (no [Q,Nk] matrix)."""

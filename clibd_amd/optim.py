@@ -68,6 +68,20 @@ class FusedAdamW(torch.optim.Optimizer):
         g = self.param_groups[0]
         self.step_count += 1
         b1, b2 = g["betas"]
-        ops.adamw_step(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, g["lr"], b1, b2, g["eps"], g["weight_decay"],
-                       self.step_count, self.grad_scale)
+        self._update(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, g["lr"], b1, b2, g["eps"], g["weight_decay"],
+                     self.step_count, self.grad_scale)
         return loss
+
+    def _update(self, *args):
+        ops.adamw_step(*args)
+
+
+class FusedAdam(FusedAdamW):
+    """torch.optim.Adam(weight_decay=...) on the same flat bucket: the decay is L2 added to the gradient before the moments, not AdamW's
+    decoupled shrink (the SimCLR pre-training's optimizer, reference scripts/unimodel/unimodel_training_for_image_encoder.py)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+    def _update(self, *args):
+        ops.adam_l2_step(*args)

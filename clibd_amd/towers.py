@@ -182,8 +182,19 @@ class ViTTower(_Tower):
         head = v.head
         if isinstance(head, torch.nn.Linear):
             D = head.weight.shape[0]
-            out = torch.empty((B, D), dtype=F32, device=x.device)
-            ops.gemm_nt(xn, ops.cast_bf16(_f32c(head.weight)), bias=_f32c(head.bias), out_f32=out)
+            if D % 16 == 0:
+                out = torch.empty((B, D), dtype=F32, device=x.device)
+                ops.gemm_nt(xn, ops.cast_bf16(_f32c(head.weight)), bias=_f32c(head.bias), out_f32=out)
+            else:
+                # a head width that is no multiple of the GEMM's 16 output columns (timm's 1000-class head, the SimCLR projection):
+                # zero rows pad the weight image, the extra columns are dropped
+                Dp = (D + 15) // 16 * 16
+                wp, bp = torch.zeros((Dp, H), dtype=BF16, device=x.device), torch.zeros((Dp,), dtype=F32, device=x.device)
+                wp[:D].copy_(ops.cast_bf16(_f32c(head.weight)))
+                bp[:D].copy_(_f32c(head.bias))
+                outp = torch.empty((B, Dp), dtype=F32, device=x.device)
+                ops.gemm_nt(xn, wp, bias=bp, out_f32=outp)
+                out = outp[:, :D].contiguous()
         else:
             out = xn.to(F32)
         state = dict(saved=saved, xcls=xcls, st=st, xn=xn, B=B, full=full, patches=patches if full else None) if save else None
