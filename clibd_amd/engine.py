@@ -17,6 +17,7 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import torch
@@ -101,6 +102,12 @@ def default_deterministic() -> bool:
 def _ordered(on: bool) -> dict:
     """keyword arguments selecting the fixed-order form of an ops reduction: none at all when the mode is off (calls stay as they were)"""
     return {"ordered": True} if on else {}
+
+
+def ln_param_grads(grads: dict, w, b, ordered: bool) -> dict:
+    """keyword arguments of ops.layernorm_bwd that accumulate d(gamma), d(beta) of the LayerNorm (w, b) in the same pass: none when
+    `grads` holds no bucket for them"""
+    return dict(dgamma=grads[id(w)].view(-1), dbeta=grads[id(b)].view(-1), **_ordered(ordered)) if id(w) in grads else {}
 
 
 def default_numerics() -> dict:
@@ -404,6 +411,8 @@ class TransformerStack:
         """(fp32 [M,3H] addend sum_j (x A_j^T) B_j^T over the slots j >= 1 on the q and v columns, [t_j]): the slots chain through the
         addend (each zero-operand GEMM takes the previous sum as its fp32 residual), so the layer's GEMM still rounds the whole sum once."""
         add32, ts = None, []
+        if c.slot2 is None:
+            return None, None
         for im in c.slot2:
             tj = ops.lora_down_proj(x_bf16, im["a_cat"])
             add32 = self._slot2_addend(tj, im["v_fwd"], 3 * self.H, residual=add32)
@@ -423,6 +432,57 @@ class TransformerStack:
         return self._cache[i].a_cat
 
     # ---- forward ------------------------------------------------------------------------------------------------
+    # A layer is a short sequence of shared steps — qkv, attend, proj, mlp — between its two LayerNorms; every kernel role has ONE call
+    # site below.  The steps take the layer's weight images `c`, the per-call plan `p`, the layer's fp8 scales (None = the
+    # bf16 form) and their operand buffers; they keep no buffer (what one allocates it hands back), so the layer code owns every lifetime.
+    def _qkv_fwd(self, c, fa, x, x8, ru, add32, qkv):
+        """qkv = x Wqkv^T + b + ru . V^T (rank-8 LoRA step; + add32, the further rank slots' fp32 addend): e4m3 (x8) or bf16 (x) operands"""
+        rv = c.v_fwd if ru is not None else None
+        if fa is not None:
+            ops.gemm_fp8_nt(x8, c.wqkv8, c.cs_qkv, bias=c.bqkv, rank_u=ru, rank_v=rv, out_bf16=qkv)
+        else:
+            ops.gemm_nt(x, c.wqkv, bias=c.bqkv, rank_u=ru, rank_v=rv, residual=add32, out_bf16=qkv)
+
+    def _attend(self, p, fa, qkv, o, drop=None):
+        """full-sequence attention into o (e4m3 with the projection's scale under the all-site fp8 forward).  Returns (o, att_sv): the
+        training forward of the single-pass attention backward writes this layer's own o and saves its rounding residual and the lse."""
+        o_lo = lse = None
+        if p.sp_ok:
+            o = o if p.keep else p.new(self.H, BF16)
+            o_lo, lse = p.new(self.H, BF16), torch.empty((p.B * self.heads * p.S,), dtype=F32, device=p.dev)
+        ops.attention_fwd(qkv, p.B, p.S, self.heads, p.key_mask, o, drop=drop, out_fp8_scale=fa["proj_in"] if fa is not None else 0.0,
+                          lse=lse, o_lo=o_lo)
+        return o, (dict(o_att=o, o_lo=o_lo, lse=lse) if p.sp_ok else None)
+
+    def _proj_fwd(self, p, c, fa, o, res, out, drop=None, fold_to=None):
+        """out = [dropout](o Wo^T + b) + res (fp32).  fold_to = (x bf16, stats): the producer of the norm2 -> fc1 fold — the LayerNorm never
+        makes a pass of its own: the projection also writes bf16(out) and its row sums, a small kernel turns those into (mean, rstd) —
+        what the LayerNorm backward reads — and fc1 applies them to (x . (gamma o W1)^T) in its epilogue (_mlp_fwd)."""
+        if fa is not None:
+            ops.gemm_fp8_nt(o, c.wo8, c.cs_o, bias=c.bo, residual=res, out_f32=out, drop=drop)
+            return
+        xb, st = fold_to if fold_to is not None else (None, None)
+        ops.gemm_nt(o, c.wo, bias=c.bo, residual=res, out_f32=out, drop=drop, out_bf16=xb,
+                    row_sums=p.fold_sums if xb is not None else None)
+        if xb is not None:
+            ops.rowsum_finalize(p.fold_sums, self.eps, st)
+
+    def _mlp_fwd(self, p, c, f8, x, res, out, h, a, drop=None, fold_st=None):
+        """a = gelu(x W1^T + b1) with gelu' saved into h (all the backward needs); out = [dropout](a W2^T + b2) + res.  The fp8 fc1 and the
+        fold's consumer epilogue (fold_st = the row statistics) always write gelu': into the scratch buffer when nothing is saved."""
+        if f8 is not None:
+            ops.gemm_fp8_nt(x, c.w18, c.cs_1, bias=c.b1, gelu_out_fp8=a, gelu_out_scale=f8["fc2_in"],
+                            out_pre=h if h is not None else p.h_tmp)
+            ops.gemm_fp8_nt(a, c.w28, c.cs_2, bias=c.b2, residual=res, out_f32=out, drop=drop)
+            return
+        if fold_st is not None:
+            w1, b1, act, pre = c.w1g, c.b1f, ops.ACT_GELU_SAVE_GRAD, h if h is not None else p.h_tmp
+            kw = dict(row_stats=fold_st, col_sum_w=c.s1)
+        else:
+            w1, b1, act, pre, kw = c.w1, c.b1, p.act_save if h is not None else ops.ACT_GELU, h, {}
+        ops.gemm_nt(x, w1, bias=b1, act=act, out_pre=pre, out_bf16=a, **kw)
+        ops.gemm_nt(a, c.w2, bias=c.b2, residual=res, out_f32=out, drop=drop)
+
     def forward(self, x_f32, x_bf16, t0, B: int, S: int, key_mask, save: bool, cls_only_last: bool = False, drop=None, full: bool = False,
                 x_fp8=None):
         """x_f32 [M,H] residual stream entering layer 0.  Post-LN stacks also pass its bf16 image and the layer-0
@@ -433,25 +493,23 @@ class TransformerStack:
         drop (post-LN only): (p_hidden, p_attention, base_seed) — HF BERT train-mode dropout; site seeds via ops.derive_seed.
         full: full fine-tune mode — every layer keeps its own attention output, MLP input and GELU output (the X operands of
         the weight gradients) instead of sharing temporaries; under the fp8 MLP-pair selection the MLP input and GELU output are the
-        e4m3 images the fp8 GEMMs consumed, recorded with their scales (xn2_s / x1_s, a_s).
+        e4m3 images the fp8 GEMMs consumed, recorded with their scales (x_mlp_s, a_s).
         x_fp8 (post-LN, fp8-forward mode): the e4m3 image of x (scale fp8[0]["qkv_in"]) from the embedding LayerNorm."""
         H, FF, M = self.H, self.FF, B * S
         dev = x_f32.device
-        saved = []
-        new = lambda cols, dt: torch.empty((M, cols), dtype=dt, device=dev)
+        new = lambda cols, dt, rows=M: torch.empty((rows, cols), dtype=dt, device=dev)
         keep = save and full
         f8s = self.fp8
-        mlp_only = f8s is not None and "qkv_in" not in f8s[0]   # fp8 site selection: QKV / attention / projection stay bf16
-        if f8s is not None and full and not mlp_only:
+        mode = None if f8s is None else ("all" if "qkv_in" in f8s[0] else "mlp")   # "mlp": QKV / attention / projection stay bf16
+        if mode == "all" and full:
             raise NotSupportedYet("fp8 forward on every site with trainable base weights (the MLP-pair selection is built)")
         cal = self._calib if f8s is None else None      # calibration pass: bf16 forward recording max |operand| per site
         amax = lambda t_: t_.abs().amax().float()
-        f8 = None
         AT = ops.FP8 if f8s is not None else BF16    # dtype of the GEMM-operand temporaries
-        o = None if keep else new(H, BF16 if mlp_only else AT)   # attention output (temporary, reused by every layer)
+        o = None if keep else new(H, BF16 if mode == "mlp" else AT)   # attention output (temporary, reused by every layer)
         a = None if keep else new(FF, AT)           # post-GELU activation (temporary)
         xn2 = new(H, AT) if (self.pre_ln and not keep) else None
-        xn8 = new(H, ops.FP8) if (f8s is not None and not mlp_only) else None   # fp8 image of the first LayerNorm's output (temporary)
+        xn8 = new(H, ops.FP8) if mode == "all" else None   # fp8 image of the first LayerNorm's output (temporary)
         # storage of gelu'(fc1 out): bf16 (default), one byte, or (round 6) the 12-bit e4m7 form of the bf16 value; the fp8-forward fc1
         # and the LN -> fc1 fold's consumer epilogue write bf16 only
         gg = self.numerics["gelu_grad"]
@@ -461,117 +519,83 @@ class TransformerStack:
         HC = 3 * FF // 2 if gg == "e4m7" else FF                                                     # columns of that buffer
         act_save = {"bf16": ops.ACT_GELU_SAVE_GRAD, "u8": ops.ACT_GELU_SAVE_GRAD_U8, "e4m7": ops.ACT_GELU_SAVE_GRAD_E12}[gg]
         h_tmp = new(FF, BF16) if (f8s is not None and not save) else None       # the fp8 fc1 form always writes gelu'
-        t = t0
         sp_ok = save and key_mask is None and f8s is None and S <= 224 and self.numerics["attn_bwd"] == "sp"
         # norm2 -> fc1 as the algebraic fold (numerics ln_fold): pre-LN, frozen base, bf16 forward, shapes the 256x256 kernel takes
-        fold = (self.pre_ln and self.numerics["ln_fold"] == "on" and self._cache[0].w1g is not None and f8s is None and not full and GG == BF16 and H % 256 == 0 and FF % 256 == 0
-                and M >= 1024 and ((M + 255) // 256) * (H // 256) >= 128 and H % 128 == 0)
+        fold = (self.pre_ln and self.numerics["ln_fold"] == "on" and self._cache[0].w1g is not None and f8s is None and not full
+                and GG == BF16 and H % 256 == 0 and FF % 256 == 0 and M >= 1024 and ((M + 255) // 256) * (H // 256) >= 128
+                and H % 128 == 0)
         fold_sums = torch.empty((H // 128, M, 2), dtype=F32, device=dev) if fold else None
         if fold and h_tmp is None and not save:
             h_tmp = new(FF, BF16)   # the consumer epilogue always writes gelu' (eval forward: into a scratch buffer)
+        p = SimpleNamespace(B=B, S=S, dev=dev, new=new, key_mask=key_mask, keep=keep, sp_ok=sp_ok, act_save=act_save, h_tmp=h_tmp,
+                            fold_sums=fold_sums)
+        t, saved = t0, []
         for i, (L, c) in enumerate(zip(self.layers, self._cache)):
-            has_lora = L.lora is not None
-            rec = {}
-            att_sv = None
-            t2 = None   # further rank slots' down-projections (LoRA ranks above 4): a list
+            lora = L.lora is not None
             f8 = f8s[i] if f8s is not None else None
+            fa = f8 if mode == "all" else None     # the scales of the attention half: None = its bf16 form
             crec = {} if cal is not None else None
+            rec = {}     # what the backward needs of this layer (filled under `save`)
             if keep:   # (fp8 MLP pair: the MLP's operands are the e4m3 images the weight gradients contract)
                 o, a = new(H, BF16), new(FF, AT)
                 xn2 = new(H, AT) if self.pre_ln else None
             if self.pre_ln and cls_only_last and i == len(self.layers) - 1:
+                # LN1 and QKV over all rows (the full-size GEMM of this block, fp8 under the all-site mode); the class-row remainder
+                # of the block stays bf16
                 xn = new(H, BF16)
-                st1 = torch.empty((M, 2), dtype=F32, device=dev)
-                t = torch.empty((M, 8), dtype=BF16, device=dev) if has_lora else None
+                st1 = new(2, F32)
+                t = new(8, BF16) if lora else None
                 qkv = new(3 * H, BF16)
-                if f8 is not None and not mlp_only:   # the full-size GEMM of this block; its class-row remainder stays bf16
-                    ops.layernorm_fwd(x_f32, c.g1, c.be1, self.eps, y_bf16=xn, stats=st1, lora_a=c.a_cat if has_lora else None, t_out=t,
-                                      y_fp8=xn8, fp8_scale=f8["qkv_in"])
-                    ops.gemm_fp8_nt(xn8, c.wqkv8, c.cs_qkv, bias=c.bqkv, rank_u=t, rank_v=c.v_fwd if has_lora else None, out_bf16=qkv)
-                else:
-                    ops.layernorm_fwd(x_f32, c.g1, c.be1, self.eps, y_bf16=xn, stats=st1, lora_a=c.a_cat if has_lora else None, t_out=t)
-                    add32, t2 = self._slot2_fwd(c, xn) if c.slot2 is not None else (None, None)
-                    ops.gemm_nt(xn, c.wqkv, bias=c.bqkv, rank_u=t, rank_v=c.v_fwd if has_lora else None, residual=add32, out_bf16=qkv)
-                    if crec is not None:
-                        crec["qkv_in"] = amax(xn)
-                newB = lambda cols, dt: torch.empty((B, cols), dtype=dt, device=dev)
-                o_cls = newB(H, BF16)
+                ops.layernorm_fwd(x_f32, c.g1, c.be1, self.eps, y_bf16=xn, stats=st1, lora_a=c.a_cat if lora else None, t_out=t,
+                                  y_fp8=xn8, fp8_scale=fa["qkv_in"] if fa is not None else 0.0)
+                add32, t2 = self._slot2_fwd(c, xn)
+                self._qkv_fwd(c, fa, xn, xn8, t, add32, qkv)
+                if crec is not None:
+                    crec["qkv_in"] = amax(xn)
+                o_cls = new(H, BF16, B)
                 ops.attention_fwd(qkv, B, S, self.heads, key_mask, o_cls, nq=1)
                 x_cls = ops.gather_rows(x_f32.view(B, S, H))
-                x1 = newB(H, F32)
-                ops.gemm_nt(o_cls, c.wo, bias=c.bo, residual=x_cls, out_f32=x1)
-                st2 = torch.empty((B, 2), dtype=F32, device=dev)
-                xn2c = newB(H, BF16)
+                x1 = new(H, F32, B)
+                self._proj_fwd(p, c, None, o_cls, x_cls, x1)
+                st2 = new(2, F32, B)
+                xn2c = new(H, BF16, B)
                 ops.layernorm_fwd(x1, c.g2, c.be2, self.eps, y_bf16=xn2c, stats=st2)
-                h = newB(HC, GG) if save else None
-                ac = newB(FF, BF16)
-                ops.gemm_nt(xn2c, c.w1, bias=c.b1, act=act_save if save else ops.ACT_GELU, out_pre=h, out_bf16=ac)
-                x2 = newB(H, F32)
-                ops.gemm_nt(ac, c.w2, bias=c.b2, residual=x1, out_f32=x2)
+                h = new(HC, GG, B) if save else None
+                ac = new(FF, BF16, B)
+                x2 = new(H, F32, B)
+                self._mlp_fwd(p, c, None, xn2c, x1, x2, h, ac)
                 if save:
-                    rec = dict(x_in=x_f32, st1=st1, xn=xn, t=t, t2=t2, qkv=qkv, x1=x1, st2=st2, h=h, cls_only=True)
-                    if keep:
-                        rec.update(o=o_cls, xn2=xn2c, a=ac)
+                    rec = dict(x_in=x_f32, st1=st1, x_qkv=xn, t=t, t2=t2, qkv=qkv, x1=x1, st2=st2, h=h, cls_only=True)
+                if keep:
+                    rec.update(o=o_cls, x_mlp=xn2c, a=ac)
                 x_f32 = x2
             elif self.pre_ln:
                 # xn = LN1(x) (+ t = xn·A^T);  qkv = xn Wqkv^T + b + t·B^T
                 xn = new(H, BF16)
-                st1 = torch.empty((M, 2), dtype=F32, device=dev)
-                t = torch.empty((M, 8), dtype=BF16, device=dev) if has_lora else None
+                st1 = new(2, F32)
+                t = new(8, BF16) if lora else None
                 qkv = new(3 * H, BF16)
                 x1 = new(H, F32)
-                st2 = torch.empty((M, 2), dtype=F32, device=dev)
+                st2 = new(2, F32)
                 h = new(HC, GG) if save else None        # holds gelu'(fc1 out): all the backward needs
                 x2 = new(H, F32)
-                if f8 is not None and mlp_only:   # fp8 on the MLP pair only: the attention half of the block is the bf16 path's
-                    ops.layernorm_fwd(x_f32, c.g1, c.be1, self.eps, y_bf16=xn, stats=st1, lora_a=c.a_cat if has_lora else None, t_out=t)
-                    add32, t2 = self._slot2_fwd(c, xn) if c.slot2 is not None else (None, None)
-                    ops.gemm_nt(xn, c.wqkv, bias=c.bqkv, rank_u=t, rank_v=c.v_fwd if has_lora else None, residual=add32, out_bf16=qkv)
-                    ops.attention_fwd(qkv, B, S, self.heads, key_mask, o)
-                    ops.gemm_nt(o, c.wo, bias=c.bo, residual=x_f32, out_f32=x1)
-                    ops.layernorm_fwd(x1, c.g2, c.be2, self.eps, stats=st2, y_fp8=xn2, fp8_scale=f8["fc1_in"])
-                    ops.gemm_fp8_nt(xn2, c.w18, c.cs_1, bias=c.b1, gelu_out_fp8=a, gelu_out_scale=f8["fc2_in"], out_pre=h if save else h_tmp)
-                    ops.gemm_fp8_nt(a, c.w28, c.cs_2, bias=c.b2, residual=x1, out_f32=x2)
-                elif f8 is not None:
-                    ops.layernorm_fwd(x_f32, c.g1, c.be1, self.eps, y_bf16=xn, stats=st1, lora_a=c.a_cat if has_lora else None, t_out=t,
-                                      y_fp8=xn8, fp8_scale=f8["qkv_in"])
-                    ops.gemm_fp8_nt(xn8, c.wqkv8, c.cs_qkv, bias=c.bqkv, rank_u=t, rank_v=c.v_fwd if has_lora else None, out_bf16=qkv)
-                    ops.attention_fwd(qkv, B, S, self.heads, key_mask, o, out_fp8_scale=f8["proj_in"])
-                    ops.gemm_fp8_nt(o, c.wo8, c.cs_o, bias=c.bo, residual=x_f32, out_f32=x1)
-                    ops.layernorm_fwd(x1, c.g2, c.be2, self.eps, stats=st2, y_fp8=xn2, fp8_scale=f8["fc1_in"])
-                    ops.gemm_fp8_nt(xn2, c.w18, c.cs_1, bias=c.b1, gelu_out_fp8=a, gelu_out_scale=f8["fc2_in"], out_pre=h if save else h_tmp)
-                    ops.gemm_fp8_nt(a, c.w28, c.cs_2, bias=c.b2, residual=x1, out_f32=x2)
-                else:
-                    ops.layernorm_fwd(x_f32, c.g1, c.be1, self.eps, y_bf16=xn, stats=st1, lora_a=c.a_cat if has_lora else None, t_out=t)
-                    add32, t2 = self._slot2_fwd(c, xn) if c.slot2 is not None else (None, None)
-                    ops.gemm_nt(xn, c.wqkv, bias=c.bqkv, rank_u=t, rank_v=c.v_fwd if has_lora else None, residual=add32, out_bf16=qkv)
-                    if sp_ok:   # training forward of the single-pass attention backward: this layer's o, its rounding residual, the lse
-                        o = o if keep else new(H, BF16)
-                        att_sv = dict(o_att=o, o_lo=new(H, BF16), lse=torch.empty((B * self.heads * S,), dtype=F32, device=dev))
-                        ops.attention_fwd(qkv, B, S, self.heads, None, o, lse=att_sv["lse"], o_lo=att_sv["o_lo"])
-                    else:
-                        ops.attention_fwd(qkv, B, S, self.heads, key_mask, o)
-                    if fold and cal is None:
-                        # norm2 never makes a pass of its own: the projection writes x1, bf16(x1) (into the xn2 temporary) and its row
-                        # sums; (mean, rstd) -> st2 (what the LayerNorm backward reads); fc1 applies them to (x1b . (gamma o W1)^T)
-                        ops.gemm_nt(o, c.wo, bias=c.bo, residual=x_f32, out_f32=x1, out_bf16=xn2, row_sums=fold_sums)
-                        ops.rowsum_finalize(fold_sums, self.eps, st2)
-                        ops.gemm_nt(xn2, c.w1g, bias=c.b1f, act=ops.ACT_GELU_SAVE_GRAD, out_pre=h if save else h_tmp, out_bf16=a, row_stats=st2, col_sum_w=c.s1)
-                    else:
-                        ops.gemm_nt(o, c.wo, bias=c.bo, residual=x_f32, out_f32=x1)
-                        ops.layernorm_fwd(x1, c.g2, c.be2, self.eps, y_bf16=xn2, stats=st2)
-                        ops.gemm_nt(xn2, c.w1, bias=c.b1, act=act_save if save else ops.ACT_GELU, out_pre=h if save else None, out_bf16=a)
-                    ops.gemm_nt(a, c.w2, bias=c.b2, residual=x1, out_f32=x2)
-                    if crec is not None:
-                        crec.update(qkv_in=amax(xn), proj_in=amax(o), fc1_in=amax(xn2), fc2_in=amax(a))
+                folded = fold and cal is None
+                ops.layernorm_fwd(x_f32, c.g1, c.be1, self.eps, y_bf16=xn, stats=st1, lora_a=c.a_cat if lora else None, t_out=t,
+                                  y_fp8=xn8, fp8_scale=fa["qkv_in"] if fa is not None else 0.0)
+                add32, t2 = self._slot2_fwd(c, xn)
+                self._qkv_fwd(c, fa, xn, xn8, t, add32, qkv)
+                o, att_sv = self._attend(p, fa, qkv, o)
+                self._proj_fwd(p, c, fa, o, x_f32, x1, fold_to=(xn2, st2) if folded else None)
+                if not folded:
+                    ops.layernorm_fwd(x1, c.g2, c.be2, self.eps, stats=st2,
+                                      **(dict(y_bf16=xn2) if f8 is None else dict(y_fp8=xn2, fp8_scale=f8["fc1_in"])))
+                self._mlp_fwd(p, c, f8, xn2, x1, x2, h, a, fold_st=st2 if folded else None)
+                if crec is not None:
+                    crec.update(qkv_in=amax(xn), proj_in=amax(o), fc1_in=amax(xn2), fc2_in=amax(a))
                 if save:
-                    rec = dict(x_in=x_f32, st1=st1, xn=xn, t=t, t2=t2, qkv=qkv, x1=x1, st2=st2, h=h)
-                    if keep:
-                        rec.update(o=o, xn2=xn2, a=a)
-                        if f8 is not None:
-                            rec.update(xn2_s=f8["fc1_in"], a_s=f8["fc2_in"])
-                    if att_sv is not None:
-                        rec.update(att_sv)
+                    rec = dict(x_in=x_f32, st1=st1, x_qkv=xn, t=t, t2=t2, qkv=qkv, x1=x1, st2=st2, h=h, **(att_sv or {}))
+                if keep:
+                    rec.update(o=o, x_mlp=xn2, a=a, **(dict(x_mlp_s=f8["fc1_in"], a_s=f8["fc2_in"]) if f8 is not None else {}))
                 x_f32 = x2
             else:
                 d_att = d_h1 = d_h2 = None
@@ -583,66 +607,35 @@ class TransformerStack:
                 qkv = new(3 * H, BF16)
                 s1 = new(H, F32)
                 x1_f32 = new(H, F32)
-                st1 = torch.empty((M, 2), dtype=F32, device=dev)
+                st1 = new(2, F32)
                 h = new(HC, GG) if save else None
                 s2 = new(H, F32)
                 x2_f32, x2_bf16 = new(H, F32), new(H, BF16)
-                st2 = torch.empty((M, 2), dtype=F32, device=dev)
+                st2 = new(2, F32)
                 nxt = self.lora_a(i + 1)
-                t_next = torch.empty((M, 8), dtype=BF16, device=dev) if nxt is not None else None
-                ru, rv = (t if has_lora else None), (c.v_fwd if has_lora else None)
-                if f8 is not None and mlp_only:   # fp8 on the MLP pair only (round 5): the attention half is the bf16 path's, LayerNorm 1 feeds fc1 as e4m3
-                    x1_bf16 = None
-                    x18 = new(H, ops.FP8)
-                    ops.gemm_nt(x_bf16, c.wqkv, bias=c.bqkv, rank_u=ru, rank_v=rv, out_bf16=qkv)
-                    ops.attention_fwd(qkv, B, S, self.heads, key_mask, o, drop=d_att)
-                    ops.gemm_nt(o, c.wo, bias=c.bo, residual=x_f32, out_f32=s1, drop=d_h1)
-                    ops.layernorm_fwd(s1, c.g1, c.be1, self.eps, y_f32=x1_f32, stats=st1, y_fp8=x18, fp8_scale=f8["fc1_in"])
-                    ops.gemm_fp8_nt(x18, c.w18, c.cs_1, bias=c.b1, gelu_out_fp8=a, gelu_out_scale=f8["fc2_in"], out_pre=h if save else h_tmp)
-                    ops.gemm_fp8_nt(a, c.w28, c.cs_2, bias=c.b2, residual=x1_f32, out_f32=s2, drop=d_h2)
-                    ops.layernorm_fwd(s2, c.g2, c.be2, self.eps, y_bf16=x2_bf16, y_f32=x2_f32, stats=st2, lora_a=nxt, t_out=t_next)
-                elif f8 is not None:
-                    if x_fp8 is None:
-                        raise ValueError("fp8 forward (post-LN): the caller passes the e4m3 image of x")
-                    x1_bf16 = None
-                    x18 = xn8
-                    ops.gemm_fp8_nt(x_fp8, c.wqkv8, c.cs_qkv, bias=c.bqkv, rank_u=ru, rank_v=rv, out_bf16=qkv)
-                    ops.attention_fwd(qkv, B, S, self.heads, key_mask, o, drop=d_att, out_fp8_scale=f8["proj_in"])
-                    ops.gemm_fp8_nt(o, c.wo8, c.cs_o, bias=c.bo, residual=x_f32, out_f32=s1, drop=d_h1)
-                    ops.layernorm_fwd(s1, c.g1, c.be1, self.eps, y_f32=x1_f32, stats=st1, y_fp8=x18, fp8_scale=f8["fc1_in"])
-                    ops.gemm_fp8_nt(x18, c.w18, c.cs_1, bias=c.b1, gelu_out_fp8=a, gelu_out_scale=f8["fc2_in"], out_pre=h if save else h_tmp)
-                    ops.gemm_fp8_nt(a, c.w28, c.cs_2, bias=c.b2, residual=x1_f32, out_f32=s2, drop=d_h2)
-                    x8_next = new(H, ops.FP8)
-                    ops.layernorm_fwd(s2, c.g2, c.be2, self.eps, y_bf16=x2_bf16, y_f32=x2_f32, stats=st2, lora_a=nxt, t_out=t_next,
-                                      y_fp8=x8_next, fp8_scale=f8s[min(i + 1, len(f8s) - 1)]["qkv_in"])
-                    x_fp8 = x8_next
-                else:
-                    x1_bf16 = new(H, BF16)
-                    add32, t2 = self._slot2_fwd(c, x_bf16) if c.slot2 is not None else (None, None)
-                    ops.gemm_nt(x_bf16, c.wqkv, bias=c.bqkv, rank_u=ru, rank_v=rv, residual=add32, out_bf16=qkv)
-                    if sp_ok:
-                        o = o if keep else new(H, BF16)
-                        att_sv = dict(o_att=o, o_lo=new(H, BF16), lse=torch.empty((B * self.heads * S,), dtype=F32, device=dev))
-                        ops.attention_fwd(qkv, B, S, self.heads, None, o, drop=d_att, lse=att_sv["lse"], o_lo=att_sv["o_lo"])
-                    else:
-                        ops.attention_fwd(qkv, B, S, self.heads, key_mask, o, drop=d_att)
-                    ops.gemm_nt(o, c.wo, bias=c.bo, residual=x_f32, out_f32=s1, drop=d_h1)
-                    ops.layernorm_fwd(s1, c.g1, c.be1, self.eps, y_bf16=x1_bf16, y_f32=x1_f32, stats=st1)
-                    ops.gemm_nt(x1_bf16, c.w1, bias=c.b1, act=act_save if save else ops.ACT_GELU, out_pre=h if save else None, out_bf16=a)
-                    ops.gemm_nt(a, c.w2, bias=c.b2, residual=x1_f32, out_f32=s2, drop=d_h2)
-                    ops.layernorm_fwd(s2, c.g2, c.be2, self.eps, y_bf16=x2_bf16, y_f32=x2_f32, stats=st2, lora_a=nxt, t_out=t_next)
-                    if crec is not None:
-                        crec.update(qkv_in=amax(x_bf16), proj_in=amax(o), fc1_in=amax(x1_bf16), fc2_in=amax(a))
+                t_next = new(8, BF16) if nxt is not None else None
+                if fa is not None and x_fp8 is None:
+                    raise ValueError("fp8 forward (post-LN): the caller passes the e4m3 image of x")
+                # the MLP's input: LayerNorm 1 writes it as bf16, or as e4m3 under either fp8 mode (round 5: also on the MLP pair only)
+                x_mlp = new(H, BF16) if f8 is None else (xn8 if fa is not None else new(H, ops.FP8))
+                add32, t2 = self._slot2_fwd(c, x_bf16)
+                self._qkv_fwd(c, fa, x_bf16, x_fp8, t if lora else None, add32, qkv)
+                o, att_sv = self._attend(p, fa, qkv, o, drop=d_att)
+                self._proj_fwd(p, c, fa, o, x_f32, s1, drop=d_h1)
+                ops.layernorm_fwd(s1, c.g1, c.be1, self.eps, y_f32=x1_f32, stats=st1,
+                                  **(dict(y_bf16=x_mlp) if f8 is None else dict(y_fp8=x_mlp, fp8_scale=f8["fc1_in"])))
+                self._mlp_fwd(p, c, f8, x_mlp, x1_f32, s2, h, a, drop=d_h2)
+                x8_next = new(H, ops.FP8) if fa is not None else None     # the next layer's QKV operand, at that layer's scale
+                ops.layernorm_fwd(s2, c.g2, c.be2, self.eps, y_bf16=x2_bf16, y_f32=x2_f32, stats=st2, lora_a=nxt, t_out=t_next,
+                                  y_fp8=x8_next, fp8_scale=f8s[min(i + 1, len(f8s) - 1)]["qkv_in"] if fa is not None else 0.0)
+                if crec is not None:
+                    crec.update(qkv_in=amax(x_bf16), proj_in=amax(o), fc1_in=amax(x_mlp), fc2_in=amax(a))
                 if save:
-                    rec = dict(x_bf16=x_bf16, t=t if has_lora else None, t2=t2, qkv=qkv, s1=s1, st1=st1, h=h, s2=s2, st2=st2,
-                               d_att=d_att, d_h1=d_h1, d_h2=d_h2)
-                    if keep:
-                        rec.update(o=o, x1_bf16=x1_bf16, a=a)
-                        if f8 is not None:
-                            rec.update(x1_bf16=x18, x1_s=f8["fc1_in"], a_s=f8["fc2_in"])
-                    if att_sv is not None:
-                        rec.update(att_sv)
-                x_f32, x_bf16, t = x2_f32, x2_bf16, t_next
+                    rec = dict(x_qkv=x_bf16, t=t if lora else None, t2=t2, qkv=qkv, s1=s1, st1=st1, h=h, s2=s2, st2=st2,
+                               d_att=d_att, d_h1=d_h1, d_h2=d_h2, **(att_sv or {}))
+                if keep:
+                    rec.update(o=o, x_mlp=x_mlp, a=a, **(dict(x_mlp_s=f8["fc1_in"], a_s=f8["fc2_in"]) if f8 is not None else {}))
+                x_f32, x_bf16, t, x_fp8 = x2_f32, x2_bf16, t_next, x8_next
             saved.append(rec)
             if cal is not None:
                 cal.append(crec)
@@ -654,6 +647,81 @@ class TransformerStack:
         L = self.layers[i]
         return L.frozen() + (L.lora.tensors() if L.lora is not None else [])
 
+    # The backward's steps, mirror images of the forward's (mlp, proj, qkv and ONE LayerNorm-backward helper), take the layer's parameter
+    # handles L, its weight images c, its saved record and the per-call plan p.  A gradient operand is a bf16 matrix `dy` and, under the
+    # 8-bit dgrad, also `dy8` = (e4m3 rows, one dequantisation factor per row) as the LayerNorm backward before it wrote them.
+    def _wgrad(self, p, dy, x, ws, bs, xs=None):
+        """full fine-tune: weight / bias gradients of one Linear (fp8 forward, MLP pair: x is the e4m3 GEMM input, xs its scale)"""
+        if p.full:
+            linear_wgrad(dy, x, ws, bs, p.grads, x_scale=xs, **_ordered(p.det))
+
+    def _ln_bwd(self, p, dy, x, st, gamma, w, b, *, dres=None, f32=False, bf16=False, res16=False, q8=False, drop=None):
+        """One LayerNorm backward: dx = LN'(dy) [+ dres, fp32 or bf16 by its dtype], written in each requested form.  Returns
+        (dx_f32, dx_bf16, dx_res_bf16, dx8): fp32; bf16 (carrying the dropout mask of `drop`); the un-dropped bf16 residual copy of the
+        post-LN bf16 stream; the (e4m3 rows, row dequantisation factors) pair the 8-bit dgrad GEMMs take.  Full fine-tune: d(gamma) and
+        d(beta) accumulate in the same pass (the kernel holds dy and xhat anyway)."""
+        mk = lambda dt: torch.empty(x.shape, dtype=dt, device=x.device)
+        # (allocated in the order these forms always were: the caching allocator's block reuse, and the peak it reports, follow it)
+        dx_f32 = mk(F32) if f32 else None
+        dx_bf16 = mk(BF16) if bf16 and not res16 else None
+        dx_res = mk(BF16) if res16 else None
+        dx8 = (mk(torch.uint8).view(ops.FP8), torch.empty((x.shape[0],), dtype=F32, device=x.device)) if q8 else None
+        if bf16 and res16:
+            dx_bf16 = mk(BF16)
+        kw = {} if dres is None else {"dres" if dres.dtype == F32 else "dres_bf16": dres}
+        if q8:
+            kw.update(dx_fp8=dx8[0], row_dequant=dx8[1])
+        if p.full:
+            kw.update(ln_param_grads(p.grads, w, b, p.det))
+        ops.layernorm_bwd(dy, x, st, gamma, dx_f32=dx_f32, dx_bf16=dx_bf16, dx_res_bf16=dx_res, drop=drop, **kw)
+        return dx_f32, dx_bf16, dx_res, dx8
+
+    def _mlp_bwd(self, p, L, c, rec, dy, dy8, out, dh=None, **join):
+        """fc2 weight gradient; d(fc1 out) = (dy W2) o gelu' -> dh; fc1 weight gradient; out = dh W1 with the ONE epilogue that joins the
+        stream (`join`): none, act=ACT_ADD_AUX + aux (bf16 stream) or residual (fp32 stream, fp32 out).  dy8: both dgrads on e4m3 operands
+        — d(fc1 out) leaves as e4m3 with the rows' scales x c2, the fc1 dgrad divides both back out; under full fine-tune the fc2 dgrad
+        writes it once more as bf16, the operand of fc1's weight gradient.  dh: the caller's buffer (class rows) or the walk's."""
+        h = rec["h"]
+        self._wgrad(p, dy, rec.get("a"), [L.fc2_w], [L.fc2_b], rec.get("a_s"))
+        if dy8 is not None:
+            p.dh8 = p.new(self.FF, torch.uint8).view(ops.FP8)
+        if dh is None and (dy8 is None or p.full):
+            dh = p.dh = p.new(self.FF, BF16) if p.dh is None else p.dh
+        if dy8 is not None:
+            ops.gemm_fp8_dgrad_nt(dy8[0], c.w2_t8, c.cs_2t, aux=h, act=_mul_aux_act(h, self.FF), out_fp8=p.dh8, out_fp8_scale=c.c2,
+                                  a_row_dequant=dy8[1] if p.full else None, out_bf16_dual=dh if p.full else None)
+        else:
+            ops.gemm_nt(dy, c.w2_t, act=_mul_aux_act(h, self.FF), aux=h, out_bf16=dh)
+        self._wgrad(p, dh, rec.get("x_mlp"), [L.fc1_w], [L.fc1_b], rec.get("x_mlp_s"))
+        if dy8 is not None:
+            ops.gemm_fp8_dgrad_nt(p.dh8, c.w1_t8, c.cs_1t, a_row_dequant=dy8[1], out_bf16=out, **join)
+        else:
+            ops.gemm_nt(dh, c.w1_t, **{"out_f32" if out.dtype == F32 else "out_bf16": out}, **join)
+
+    def _proj_bwd(self, p, L, c, rec, dy, dy8, out):
+        """projection weight gradient; out = d(attention out) = dy Wo (bf16)"""
+        self._wgrad(p, dy, rec.get("o"), [L.proj_w], [L.proj_b])
+        if dy8 is not None:
+            ops.gemm_fp8_dgrad_nt(dy8[0], c.wo_t8, c.cs_ot, a_row_dequant=dy8[1], out_bf16=out)
+        else:
+            ops.gemm_nt(dy, c.wo_t, out_bf16=out)
+
+    def _qkv_bwd(self, p, L, c, rec, dqkv, dt, out=None, new_out=None, residual=None, **join):
+        """adapter gradients (+ dt, the rank-8 operand of the dgrad), QKV weight gradient, then — unless nothing trainable lies below
+        (neither `out` nor `new_out`) — the QKV dgrad dqkv Wqkv + dt . V^T [+ the further rank slots' fp32 addend] with the epilogue
+        that joins the stream, into `out` or a fresh [M,H] matrix of dtype `new_out`; returns it."""
+        lora = L.lora is not None
+        dt2 = self._lora_grads(L, c, dqkv, rec["x_qkv"], rec["t"], dt, p.grads, rec.get("t2")) if lora else None
+        self._wgrad(p, dqkv, rec["x_qkv"], L.qkv_w, L.qkv_b)
+        if out is None and new_out is None:
+            return None
+        # further rank slots: sum_j dt_j . A_cat_j, fp32 (held on the plan until the next layer's replaces it)
+        add32 = p.add32 = residual if dt2 is None else self._slot2_bwd_addend(c, dt2, residual=residual)
+        out = p.new(self.H, new_out) if out is None else out
+        ops.gemm_nt(dqkv, c.wqkv_t, rank_u=dt if lora else None, rank_v=c.v_bwd if lora else None, residual=add32,
+                    **{"out_f32" if out.dtype == F32 else "out_bf16": out}, **join)
+        return out
+
     def backward(self, dx_f32, dx_bf16, saved, B: int, S: int, key_mask, grads: dict, full: bool = False, on_layer_done=None):
         """dx = gradient w.r.t. the stack output (fp32 residual stream; pre-LN also needs its bf16 image).
         on_layer_done(i): called once layer i's parameter gradients are complete (enqueued on the current stream) — the
@@ -663,209 +731,86 @@ class TransformerStack:
         walk stops at the lowest adapted layer because nothing below it is trainable)."""
         H, FF, M = self.H, self.FF, B * S
         dev = dx_f32.device
-        new = lambda cols, dt: torch.empty((M, cols), dtype=dt, device=dev)
-        dh = None   # d(fc1 out), bf16 [M,FF]: allocated by the first layer that takes the bf16 dgrad
+        new = lambda cols, dt, rows=M: torch.empty((rows, cols), dtype=dt, device=dev)
         dtmp = new(H, BF16)
         dqkv = new(3 * H, BF16)
-        dt = torch.empty((M, 16), dtype=BF16, device=dev)
+        dt = new(16, BF16)
         first_lora = min((i for i, L in enumerate(self.layers) if L.lora is not None), default=len(self.layers))
         if full:
             first_lora = -1  # every layer has trainable parameters and the input gradient is needed
         # bf16 residual-gradient stream (see NUMERICS_CHOICES).  Round 4: full fine-tune mode takes it too — the LayerNorm parameter
-        # gradients ride along in the same kernel (clibd_layernorm_bwd with dgamma / dbeta), and the BOTTOM layer hands an fp32 gradient to the
-        # embedding backward as before (`need32`).  409.6 ms per step at b = 2048 with the fp32 stream (profiles/r04_fullft_*_v1*).
+        # gradients ride along in the same kernel (clibd_layernorm_bwd with dgamma / dbeta), and the BOTTOM layer hands an fp32 gradient to
+        # the embedding backward as before.  409.6 ms per step at b = 2048 with the fp32 stream (profiles/r04_fullft_*_v1*).
         r16 = self.numerics["residual_grad"] == "bf16"
-        # 8-bit dgrad (numerics dgrad = "fp8"): every LayerNorm backward below also writes its output as e4m3 rows + one dequantisation
-        # factor per row (new8), which the next dgrad GEMM takes as its A operand; dx8 = that pair for the incoming stream gradient
-        # Round 6: also with trainable base weights (full fine-tune, the reference's final recipe: `disable_lora: true`) — the dgrad takes the e4m3
-        # rows, every weight gradient stays bf16 (the LayerNorm backward then writes both copies, and the fc2 dgrad writes d(fc1 out) twice: e4m3
-        # for the fc1 dgrad, bf16 for the fc1 weight gradient).
-        dg8 = self._dgrad8_ok() and self._cache[0].w2_t8 is not None and M % 4 == 0 and M * FF < 2 ** 32   # (the fp8 kernel addresses operands with 32-bit byte offsets)
-        new8 = lambda cols: (torch.empty((M, cols), dtype=torch.uint8, device=dev).view(ops.FP8), torch.empty((M,), dtype=F32, device=dev))
-        f8kw = lambda pair: dict(dx_fp8=pair[0], row_dequant=pair[1])
+        # 8-bit dgrad (numerics dgrad = "fp8"): the LayerNorm backwards below also write their output as e4m3 rows + one dequantisation
+        # factor per row, which the next dgrad GEMM takes as its A operand; dx8 = that pair for the incoming stream gradient.
+        # Round 6: also with trainable base weights (full fine-tune, the reference's final recipe: `disable_lora: true`) — the dgrad takes
+        # the e4m3 rows, every weight gradient stays bf16 (the LayerNorm backward then writes both copies, and the fc2 dgrad writes
+        # d(fc1 out) twice: e4m3 for the fc1 dgrad, bf16 for the fc1 weight gradient).
+        dg8 = (self._dgrad8_ok() and self._cache[0].w2_t8 is not None and M % 4 == 0
+               and M * FF < 2 ** 32)   # (the fp8 kernel addresses operands with 32-bit byte offsets)
+        q8_mlp, q8_proj = dg8 and "mlp" in self.dgrad8_sites, dg8 and "proj" in self.dgrad8_sites   # (pre-LN: per-site selection)
         dx8 = None
-        # full fine-tune: the LayerNorm backward accumulates d(gamma), d(beta) in the same pass (it holds dy and xhat anyway)
-        det = self.deterministic
-        pg = lambda w, b: (dict(dgamma=grads[id(w)].view(-1), dbeta=grads[id(b)].view(-1), **_ordered(det))
-                           if full and id(w) in grads else {})
-        # (fp8 forward, MLP pair: rec holds the e4m3 GEMM inputs and their scales — xn2_s / x1_s, a_s — and linear_wgrad contracts those)
-        wg = lambda dy, x, ws, bs, xs=None: linear_wgrad(dy, x, ws, bs, grads, x_scale=xs, **_ordered(det)) if full else None
+        # dh = d(fc1 out), bf16 [M,FF]: allocated by the first layer that takes the bf16 dgrad; dh8 = its e4m3 form, per layer
+        p = SimpleNamespace(dev=dev, new=new, grads=grads, full=full, det=self.deterministic, dh=None, dh8=None, add32=None)
+        # post-LN: `dx_f32` holds the incoming gradient of the layer output (fp32 from the head at the top layer; below it bf16 on the bf16
+        # stream).  bf16 stream: each LayerNorm backward writes the un-dropped residual copy (res) and, under dropout, the masked copy
+        # the dense branch consumes — not at all where the dgrad takes the e4m3 rows and no weight gradient wants it — and the two dgrads
+        # that re-join the stream add the residual copy in their epilogue (ACT_ADD_AUX).  fp32 stream: the LayerNorm backward writes
+        # fp32 + (masked) bf16 and the joining dgrads take the fp32 copy as their residual.
+        dropped = lambda d: d is not None and d.thr16 > 0
+        ln = lambda dy, x, st, g, w, b, d: self._ln_bwd(p, dy, x, st, g, w, b, drop=d, **(
+            dict(res16=True, bf16=dropped(d) and (full or not dg8), q8=dg8) if r16 else dict(f32=True, bf16=True)))
+        join = lambda f32, res: dict(act=ops.ACT_ADD_AUX, aux=res) if r16 else dict(residual=f32)
         for i in range(len(self.layers) - 1, -1, -1):
             L, c, rec = self.layers[i], self._cache[i], saved[i]
-            has_lora = L.lora is not None
-            dt2 = None   # further rank slots' dt (LoRA ranks above 4): a list, set by _lora_grads
             if i < first_lora:
                 break  # nothing trainable at or below this layer
-            if self.pre_ln and rec.get("cls_only"):
-                # dx_f32 / dx_bf16 are [B,H]: the gradient of the class-token row of this block's output
-                newB = lambda cols, dt: torch.empty((B, cols), dtype=dt, device=dev)
-                dhc, dtc = newB(FF, BF16), newB(H, BF16)
-                wg(dx_bf16, rec.get("a"), [L.fc2_w], [L.fc2_b])
-                ops.gemm_nt(dx_bf16, c.w2_t, act=_mul_aux_act(rec["h"], FF), aux=rec["h"], out_bf16=dhc)
-                wg(dhc, rec.get("xn2"), [L.fc1_w], [L.fc1_b])
-                ops.gemm_nt(dhc, c.w1_t, out_bf16=dtc)
-                dx1_f32, dx1_bf16 = newB(H, F32), newB(H, BF16)
-                ops.layernorm_bwd(dtc, rec["x1"], rec["st2"], c.g2, dres=dx_f32, dx_f32=dx1_f32, dx_bf16=dx1_bf16, **pg(L.ln2_w, L.ln2_b))
-                wg(dx1_bf16, rec.get("o"), [L.proj_w], [L.proj_b])
-                ops.gemm_nt(dx1_bf16, c.wo_t, out_bf16=dtc)                                              # d(attn out), class rows
-                ops.attention_bwd(rec["qkv"], dtc, B, S, self.heads, key_mask, dqkv, nq=1)
-                if has_lora:
-                    dt2 = self._lora_grads(L, c, dqkv, rec["xn"], rec["t"], dt, grads, rec.get("t2"))
-                wg(dqkv, rec["xn"], L.qkv_w, L.qkv_b)
-                if i > first_lora:
-                    add32 = None if dt2 is None else self._slot2_bwd_addend(c, dt2)      # further rank slots: sum_j dt_j . A_cat_j, fp32
-                    ops.gemm_nt(dqkv, c.wqkv_t, rank_u=dt if has_lora else None, rank_v=c.v_bwd if has_lora else None, residual=add32, out_bf16=dtmp)
-                    if r16:
-                        dres16, _ = ops.scatter_rows(dx1_f32, S, bf16=True, f32=False)           # residual path: class rows only
-                        ndx_bf16 = new(H, BF16)
-                        ndx_f32 = new(H, F32) if (full and i == 0) else None
-                        dx8 = new8(H) if (dg8 and "mlp" in self.dgrad8_sites) else None
-                        ops.layernorm_bwd(dtmp, rec["x_in"], rec["st1"], c.g1, dres_bf16=dres16, dx_bf16=ndx_bf16, dx_f32=ndx_f32, **pg(L.ln1_w, L.ln1_b),
-                                          **(f8kw(dx8) if dx8 is not None else {}))
-                        dx_f32, dx_bf16 = ndx_f32, ndx_bf16
-                    else:
-                        _, dres_full = ops.scatter_rows(dx1_f32, S, bf16=False, f32=True)        # residual path: class rows only
-                        ndx_f32, ndx_bf16 = new(H, F32), new(H, BF16)
-                        ops.layernorm_bwd(dtmp, rec["x_in"], rec["st1"], c.g1, dres=dres_full, dx_f32=ndx_f32, dx_bf16=ndx_bf16, **pg(L.ln1_w, L.ln1_b))
-                        dx_f32, dx_bf16 = ndx_f32, ndx_bf16
-            elif self.pre_ln:
-                wg(dx_bf16, rec.get("a"), [L.fc2_w], [L.fc2_b], rec.get("a_s"))
-                if dg8 and dx8 is not None:   # d(fc1 out) leaves as e4m3 with the rows' scales x c2; the fc1 dgrad divides both back out
-                    dh8 = torch.empty((M, FF), dtype=torch.uint8, device=dev).view(ops.FP8)
-                    if full:   # ... and once more as bf16: the operand of fc1's weight gradient
-                        dh = new(FF, BF16) if dh is None else dh
-                    ops.gemm_fp8_dgrad_nt(dx8[0], c.w2_t8, c.cs_2t, aux=rec["h"], act=_mul_aux_act(rec["h"], FF), out_fp8=dh8, out_fp8_scale=c.c2,
-                                          a_row_dequant=dx8[1] if full else None, out_bf16_dual=dh if full else None)
-                    wg(dh, rec.get("xn2"), [L.fc1_w], [L.fc1_b], rec.get("xn2_s"))
-                    ops.gemm_fp8_dgrad_nt(dh8, c.w1_t8, c.cs_1t, a_row_dequant=dx8[1], out_bf16=dtmp)
+            down = i > first_lora     # something trainable lies below: the gradient of this layer's input is needed
+            if self.pre_ln:
+                need32 = not r16 or (full and i == 0)
+                if rec.get("cls_only"):
+                    # dx_f32 / dx_bf16 are [B,H]: the gradient of the class-token row of this block's output
+                    dhc, dtc = new(FF, BF16, B), new(H, BF16, B)
+                    self._mlp_bwd(p, L, c, rec, dx_bf16, None, dtc, dh=dhc)
+                    dx1_f32, dx1_bf16, _, _ = self._ln_bwd(p, dtc, rec["x1"], rec["st2"], c.g2, L.ln2_w, L.ln2_b, dres=dx_f32,
+                                                           f32=True, bf16=True)
+                    self._proj_bwd(p, L, c, rec, dx1_bf16, None, dtc)                                    # d(attn out), class rows
+                    self._attention_bwd(rec, dtc, B, S, key_mask, dqkv, nq=1)
                 else:
-                    dh = new(FF, BF16) if dh is None else dh
-                    ops.gemm_nt(dx_bf16, c.w2_t, act=_mul_aux_act(rec["h"], FF), aux=rec["h"], out_bf16=dh)      # d(fc1 out)
-                    wg(dh, rec.get("xn2"), [L.fc1_w], [L.fc1_b], rec.get("xn2_s"))
-                    ops.gemm_nt(dh, c.w1_t, out_bf16=dtmp)                                               # d(LN2 out)
-                dx18 = new8(H) if (dg8 and "proj" in self.dgrad8_sites) else None
-                if r16:
-                    dx1_f32, dx1_bf16 = None, new(H, BF16)
-                    ops.layernorm_bwd(dtmp, rec["x1"], rec["st2"], c.g2, dres_bf16=dx_bf16, dx_bf16=dx1_bf16, **pg(L.ln2_w, L.ln2_b),
-                                      **(f8kw(dx18) if dx18 is not None else {}))
-                else:
-                    dx1_f32, dx1_bf16 = new(H, F32), new(H, BF16)
-                    ops.layernorm_bwd(dtmp, rec["x1"], rec["st2"], c.g2, dres=dx_f32, dx_f32=dx1_f32, dx_bf16=dx1_bf16, **pg(L.ln2_w, L.ln2_b))
-                wg(dx1_bf16, rec.get("o"), [L.proj_w], [L.proj_b])
-                if dx18 is not None:
-                    ops.gemm_fp8_dgrad_nt(dx18[0], c.wo_t8, c.cs_ot, a_row_dequant=dx18[1], out_bf16=dtmp)   # d(attn out)
-                else:
-                    ops.gemm_nt(dx1_bf16, c.wo_t, out_bf16=dtmp)                                         # d(attn out)
-                self._attention_bwd(rec, dtmp, B, S, key_mask, dqkv)
-                if has_lora:
-                    dt2 = self._lora_grads(L, c, dqkv, rec["xn"], rec["t"], dt, grads, rec.get("t2"))
-                wg(dqkv, rec["xn"], L.qkv_w, L.qkv_b)
-                if i > first_lora:
-                    add32 = None if dt2 is None else self._slot2_bwd_addend(c, dt2)      # further rank slots: sum_j dt_j . A_cat_j, fp32
-                    ops.gemm_nt(dqkv, c.wqkv_t, rank_u=dt if has_lora else None, rank_v=c.v_bwd if has_lora else None, residual=add32, out_bf16=dtmp)
-                    if r16:
-                        ndx_f32, ndx_bf16 = (new(H, F32) if (full and i == 0) else None), new(H, BF16)
-                        dx8 = new8(H) if (dg8 and "mlp" in self.dgrad8_sites) else None
-                        ops.layernorm_bwd(dtmp, rec["x_in"], rec["st1"], c.g1, dres_bf16=dx1_bf16, dx_bf16=ndx_bf16, dx_f32=ndx_f32, **pg(L.ln1_w, L.ln1_b),
-                                          **(f8kw(dx8) if dx8 is not None else {}))
-                    else:
-                        ndx_f32, ndx_bf16 = new(H, F32), new(H, BF16)
-                        ops.layernorm_bwd(dtmp, rec["x_in"], rec["st1"], c.g1, dres=dx1_f32, dx_f32=ndx_f32, dx_bf16=ndx_bf16, **pg(L.ln1_w, L.ln1_b))
-                    dx_f32, dx_bf16 = ndx_f32, ndx_bf16
-            elif r16:
-                # post-LN, bf16 stream: `dx_f32` holds the incoming gradient of the layer output (fp32 from the head at the top layer,
-                # bf16 below).  Each LayerNorm backward writes the un-dropped residual copy (*_res) and, under dropout, the masked
-                # copy the dense branch's dgrad consumes; the two dgrads that re-join the stream add the residual copy in their epilogue.
-                def ln_back(dy, xs, st, gam, drop_site, pgk):
-                    res = new(H, BF16)
-                    if dg8 and full:   # the dgrad takes the e4m3 rows, the weight gradient the (masked) bf16 copy; parameter gradients ride along
-                        q8 = new8(H)
-                        dropped = drop_site is not None and drop_site.thr16 > 0
-                        masked = new(H, BF16) if dropped else None
-                        ops.layernorm_bwd(dy, xs, st, gam, dx_res_bf16=res, dx_bf16=masked, drop=drop_site, **pgk, **f8kw(q8))
-                        return res, (masked if dropped else res), q8
-                    if dg8:   # the dense branch's dgrad takes the e4m3 rows: the masked bf16 copy is not written at all
-                        q8 = new8(H)
-                        ops.layernorm_bwd(dy, xs, st, gam, dx_res_bf16=res, drop=drop_site, **f8kw(q8))
-                        return res, None, q8
-                    if drop_site is not None and drop_site.thr16 > 0:
-                        masked = new(H, BF16)
-                        ops.layernorm_bwd(dy, xs, st, gam, dx_res_bf16=res, dx_bf16=masked, drop=drop_site, **pgk)
-                        return res, masked, None
-                    ops.layernorm_bwd(dy, xs, st, gam, dx_res_bf16=res, **pgk)
-                    return res, res, None
-
-                ds2_res, ds2_b, ds2_8 = ln_back(dx_f32, rec["s2"], rec["st2"], c.g2, rec["d_h2"], pg(L.ln2_w, L.ln2_b))
-                dx1 = new(H, BF16)
-                if dg8:
-                    dh8 = torch.empty((M, FF), dtype=torch.uint8, device=dev).view(ops.FP8)
-                    if full:
-                        wg(ds2_b, rec.get("a"), [L.fc2_w], [L.fc2_b], rec.get("a_s"))
-                        dh = new(FF, BF16) if dh is None else dh
-                    ops.gemm_fp8_dgrad_nt(ds2_8[0], c.w2_t8, c.cs_2t, aux=rec["h"], act=_mul_aux_act(rec["h"], FF), out_fp8=dh8, out_fp8_scale=c.c2,
-                                          a_row_dequant=ds2_8[1] if full else None, out_bf16_dual=dh if full else None)
-                    wg(dh, rec.get("x1_bf16"), [L.fc1_w], [L.fc1_b], rec.get("x1_s"))
-                    ops.gemm_fp8_dgrad_nt(dh8, c.w1_t8, c.cs_1t, a_row_dequant=ds2_8[1], aux=ds2_res, act=ops.ACT_ADD_AUX, out_bf16=dx1)
-                else:
-                    dh = new(FF, BF16) if dh is None else dh
-                    wg(ds2_b, rec.get("a"), [L.fc2_w], [L.fc2_b], rec.get("a_s"))
-                    ops.gemm_nt(ds2_b, c.w2_t, act=_mul_aux_act(rec["h"], FF), aux=rec["h"], out_bf16=dh)
-                    wg(dh, rec.get("x1_bf16"), [L.fc1_w], [L.fc1_b], rec.get("x1_s"))
-                    ops.gemm_nt(dh, c.w1_t, act=ops.ACT_ADD_AUX, aux=ds2_res, out_bf16=dx1)
-                ds1_res, ds1_b, ds1_8 = ln_back(dx1, rec["s1"], rec["st1"], c.g1, rec["d_h1"], pg(L.ln1_w, L.ln1_b))
-                if dg8:
-                    wg(ds1_b, rec.get("o"), [L.proj_w], [L.proj_b])
-                    ops.gemm_fp8_dgrad_nt(ds1_8[0], c.wo_t8, c.cs_ot, a_row_dequant=ds1_8[1], out_bf16=dtmp)
-                else:
-                    wg(ds1_b, rec.get("o"), [L.proj_w], [L.proj_b])
-                    ops.gemm_nt(ds1_b, c.wo_t, out_bf16=dtmp)
-                self._attention_bwd(rec, dtmp, B, S, key_mask, dqkv, drop=rec["d_att"])
-                if has_lora:
-                    dt2 = self._lora_grads(L, c, dqkv, rec["x_bf16"], rec["t"], dt, grads, rec.get("t2"))
-                wg(dqkv, rec["x_bf16"], L.qkv_w, L.qkv_b)
-                if i > first_lora:
-                    add32 = None if dt2 is None else self._slot2_bwd_addend(c, dt2)
-                    if full and i == 0:   # the embedding backward takes an fp32 gradient (generic epilogue: one launch per tower)
-                        ndx = new(H, F32)
-                        ops.gemm_nt(dqkv, c.wqkv_t, rank_u=dt if has_lora else None, rank_v=c.v_bwd if has_lora else None,
-                                    act=ops.ACT_ADD_AUX, aux=ds1_res, residual=add32, out_f32=ndx)
-                    else:
-                        ndx = new(H, BF16)
-                        ops.gemm_nt(dqkv, c.wqkv_t, rank_u=dt if has_lora else None, rank_v=c.v_bwd if has_lora else None,
-                                    act=ops.ACT_ADD_AUX, aux=ds1_res, residual=add32, out_bf16=ndx)
-                    dx_f32 = ndx
+                    self._mlp_bwd(p, L, c, rec, dx_bf16, dx8, dtmp)                                      # d(LN2 out)
+                    dx1_f32, dx1_bf16, _, dx18 = self._ln_bwd(p, dtmp, rec["x1"], rec["st2"], c.g2, L.ln2_w, L.ln2_b,
+                                                              dres=dx_bf16 if r16 else dx_f32, f32=not r16, bf16=True, q8=q8_proj)
+                    self._proj_bwd(p, L, c, rec, dx1_bf16, dx18, dtmp)                                   # d(attn out)
+                    self._attention_bwd(rec, dtmp, B, S, key_mask, dqkv)
+                self._qkv_bwd(p, L, c, rec, dqkv, dt, out=dtmp if down else None)
+                if down:
+                    if rec.get("cls_only"):   # residual path: class rows only (never rebound: this matrix lives to the end of the walk)
+                        dres_cls = ops.scatter_rows(dx1_f32, S, bf16=r16, f32=not r16)[0 if r16 else 1]
+                    dres = dres_cls if rec.get("cls_only") else (dx1_bf16 if r16 else dx1_f32)
+                    dx_f32, dx_bf16, _, dx8 = self._ln_bwd(p, dtmp, rec["x_in"], rec["st1"], c.g1, L.ln1_w, L.ln1_b, dres=dres,
+                                                           f32=need32, bf16=True, q8=q8_mlp)
             else:
-                ds2_f32, ds2_bf16 = new(H, F32), new(H, BF16)
-                ops.layernorm_bwd(dx_f32, rec["s2"], rec["st2"], c.g2, dx_f32=ds2_f32, dx_bf16=ds2_bf16, drop=rec["d_h2"], **pg(L.ln2_w, L.ln2_b))
-                wg(ds2_bf16, rec.get("a"), [L.fc2_w], [L.fc2_b], rec.get("a_s"))
-                dh = new(FF, BF16) if dh is None else dh
-                ops.gemm_nt(ds2_bf16, c.w2_t, act=_mul_aux_act(rec["h"], FF), aux=rec["h"], out_bf16=dh)
-                wg(dh, rec.get("x1_bf16"), [L.fc1_w], [L.fc1_b], rec.get("x1_s"))
-                dx1 = new(H, F32)
-                ops.gemm_nt(dh, c.w1_t, residual=ds2_f32, out_f32=dx1)
-                ds1_f32, ds1_bf16 = new(H, F32), new(H, BF16)
-                ops.layernorm_bwd(dx1, rec["s1"], rec["st1"], c.g1, dx_f32=ds1_f32, dx_bf16=ds1_bf16, drop=rec["d_h1"], **pg(L.ln1_w, L.ln1_b))
-                wg(ds1_bf16, rec.get("o"), [L.proj_w], [L.proj_b])
-                ops.gemm_nt(ds1_bf16, c.wo_t, out_bf16=dtmp)
+                ds2_f32, ds2_b, ds2_res, ds2_8 = ln(dx_f32, rec["s2"], rec["st2"], c.g2, L.ln2_w, L.ln2_b, rec["d_h2"])
+                dx1 = new(H, BF16 if r16 else F32)
+                self._mlp_bwd(p, L, c, rec, ds2_b if ds2_b is not None else ds2_res, ds2_8, dx1, **join(ds2_f32, ds2_res))
+                ds1_f32, ds1_b, ds1_res, ds1_8 = ln(dx1, rec["s1"], rec["st1"], c.g1, L.ln1_w, L.ln1_b, rec["d_h1"])
+                self._proj_bwd(p, L, c, rec, ds1_b if ds1_b is not None else ds1_res, ds1_8, dtmp)
                 self._attention_bwd(rec, dtmp, B, S, key_mask, dqkv, drop=rec["d_att"])
-                if has_lora:
-                    dt2 = self._lora_grads(L, c, dqkv, rec["x_bf16"], rec["t"], dt, grads, rec.get("t2"))
-                wg(dqkv, rec["x_bf16"], L.qkv_w, L.qkv_b)
-                if i > first_lora:
-                    ndx = new(H, F32)
-                    res32 = ds1_f32 if dt2 is None else self._slot2_bwd_addend(c, dt2, residual=ds1_f32)
-                    ops.gemm_nt(dqkv, c.wqkv_t, rank_u=dt if has_lora else None, rank_v=c.v_bwd if has_lora else None,
-                                residual=res32, out_f32=ndx)
+                # (bf16 stream, bottom layer of a full fine-tune: the embedding backward takes an fp32 gradient)
+                ndx = self._qkv_bwd(p, L, c, rec, dqkv, dt, new_out=(F32 if not r16 or (full and i == 0) else BF16) if down else None,
+                                    **join(ds1_f32, ds1_res))
+                if down:
                     dx_f32 = ndx
             if on_layer_done is not None:
                 on_layer_done(i)
         return dx_f32 if full else None
 
-    def _attention_bwd(self, rec, dout, B, S, key_mask, dqkv, drop=None):
+    def _attention_bwd(self, rec, dout, B, S, key_mask, dqkv, drop=None, nq=None):
         if "lse" in rec:   # the forward saved what the single-pass kernel needs
             ops.attention_bwd_sp(rec["qkv"], dout, rec["o_att"], rec["o_lo"], rec["lse"], B, S, self.heads, dqkv, drop=drop)
         else:
-            ops.attention_bwd(rec["qkv"], dout, B, S, self.heads, key_mask, dqkv, drop=drop)
+            ops.attention_bwd(rec["qkv"], dout, B, S, self.heads, key_mask, dqkv, nq=nq, drop=drop)
 
     def _lora_grads(self, L, c, dqkv, x_bf16, t, dt, grads, t2=None):
         """dt[:, 0:4] = dq·B_q, dt[:, 4:8] = dv·B_v (the rank-8 operand of the QKV dgrad that follows) and the four adapter gradients

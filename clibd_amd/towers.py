@@ -13,7 +13,7 @@ from typing import List, Optional
 import torch
 
 from . import ops
-from .engine import BF16, F32, GradBucket, LayerSpec, LoraParams, NotSupportedYet, TransformerStack, _f32c, _ordered, dense_head_backward, linear_wgrad
+from .engine import BF16, F32, GradBucket, LayerSpec, LoraParams, NotSupportedYet, TransformerStack, _f32c, _ordered, dense_head_backward, linear_wgrad, ln_param_grads
 
 
 def _trainable(params):
@@ -211,7 +211,7 @@ class ViTTower(_Tower):
         dxcls_b = torch.empty((B, H), dtype=BF16, device=dout.device)
         full = state["full"]
         det = self.deterministic
-        pg = dict(dgamma=grads[id(v.norm.weight)].view(-1), dbeta=grads[id(v.norm.bias)].view(-1), **_ordered(det)) if full and id(v.norm.weight) in grads else {}
+        pg = ln_param_grads(grads, v.norm.weight, v.norm.bias, det) if full else {}
         ops.layernorm_bwd(dxn, state["xcls"], state["st"], _f32c(v.norm.weight), dx_f32=dxcls, dx_bf16=dxcls_b, **pg)
         self._ready(0)
         nl = len(self.stack.layers)
@@ -380,7 +380,7 @@ class BertTower(_Tower):
             dlogits = ops.softmax_mean_bwd(state["logits"], dout, B, S)
             dhln = dense_head_backward(dlogits, state["hln"], dec.weight, dec.bias, grads, out_bf16=True, **_ordered(det))
             full = state["full"]
-            pg = dict(dgamma=grads[id(tln.weight)].view(-1), dbeta=grads[id(tln.bias)].view(-1), **_ordered(det)) if full and id(tln.weight) in grads else {}
+            pg = ln_param_grads(grads, tln.weight, tln.bias, det) if full else {}
             dg = torch.empty((M, H), dtype=BF16, device=dev)
             ops.layernorm_bwd(dhln, state["g"], state["st"], _f32c(tln.weight), dx_bf16=dg, **pg)
             dhpre = ops.gelu_bwd(dg, state["hpre"])
@@ -403,7 +403,7 @@ class BertTower(_Tower):
             lw, lb = emb.LayerNorm.weight, emb.LayerNorm.bias
             if state["d_emb"] is not None and state["d_emb"].thr16 > 0:
                 dx0 = ops.dropout_apply(dx0, state["d_emb"])  # gradient w.r.t. the LayerNorm output
-            pg = dict(dgamma=grads[id(lw)].view(-1), dbeta=grads[id(lb)].view(-1), **_ordered(det)) if id(lw) in grads else {}
+            pg = ln_param_grads(grads, lw, lb, det)
             tabs = [emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight]
             need_de = any(id(t) in grads for t in tabs)
             if need_de or pg:
