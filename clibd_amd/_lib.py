@@ -140,6 +140,12 @@ EXT_SIGNATURES = {
     "clibd_adam_l2_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p]),
 }
 
+# the SimCLR view generator (include/clibd_hip_views.h): a third additive table, bound after the other two
+VIEW_SIGNATURES = {
+    "clibd_simclr_views_workspace_bytes": (c_size_t, [c_int]),
+    "clibd_simclr_views_u8": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -163,7 +169,7 @@ def load() -> C.CDLL:
             "clibd_amd has no CPU fallback for its compute path."
         )
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

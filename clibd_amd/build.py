@@ -21,7 +21,12 @@ INCLUDE = HERE.parent / "include"
 LIB = HERE / "libclibd_hip.so"
 OBJ = CSRC / "build"
 ARCH = "gfx950"
-SOURCES = ["capi", "gemm", "gemm256", "gemm256_tn", "layernorm", "attention", "lora", "elementwise", "loss", "topk", "paramgrad", "evalacc", "augment", "ntxent"]
+SOURCES = ["capi", "gemm", "gemm256", "gemm256_tn", "layernorm", "attention", "lora", "elementwise", "loss", "topk", "paramgrad", "evalacc", "augment", "ntxent", "views"]
+
+
+def _public_headers() -> list[Path]:
+    """the C-ABI headers: clibd_hip.h and the additive ones beside it (clibd_hip_simclr.h, clibd_hip_views.h)"""
+    return sorted(INCLUDE.glob("clibd_hip*.h"))
 
 
 def csrc_hash() -> str:
@@ -29,7 +34,7 @@ def csrc_hash() -> str:
     import hashlib
 
     h = hashlib.sha256()
-    for f in sorted(list(CSRC.glob("*.hip")) + list(CSRC.glob("*.h")) + [INCLUDE / "clibd_hip.h", INCLUDE / "clibd_hip_simclr.h"]):
+    for f in sorted(list(CSRC.glob("*.hip")) + list(CSRC.glob("*.h")) + _public_headers()):
         h.update(f.name.encode())
         h.update(f.read_bytes())
     return h.hexdigest()[:16]
@@ -43,7 +48,7 @@ def _hipcc() -> str:
 
 
 def _deps() -> list[Path]:
-    return [p for p in CSRC.glob("*.h")] + [INCLUDE / "clibd_hip.h", INCLUDE / "clibd_hip_simclr.h"]
+    return [p for p in CSRC.glob("*.h")] + _public_headers()
 
 
 def _stale(target: Path, srcs: list[Path]) -> bool:

@@ -14,23 +14,16 @@
 #include "common.h"
 #include "../../include/clibd_hip.h"
 #include "host_util.h"
+#include "augment_common.h"
 
 namespace clibd {
 namespace {
 
-constexpr int OUT = 224;        // output side
+using namespace aug;            // OUT, DOWN_MAX, RB, CAP, IPT, the weight tables and the band resample (augment_common.h)
+
 constexpr int KMAX = 128;       // composite taps per output row / column (h, w <= 384 and a resize factor <= 16 need at most 98)
 constexpr int CROP_MAX = 384;   // crop box side (RandomResizedCrop of a 256-short-side image: <= 342)
-constexpr int DOWN_MAX = 16;    // resize factor in / out per axis
-constexpr int RB = 8;           // output rows per resample workgroup
-constexpr int CAP = 16;         // horizontally filtered source rows staged in LDS at a time (16 x 224 x 3 fp32 = 42 KiB)
-constexpr int IPT = RB * OUT / 256;   // (row, column) items per thread in the vertical pass
-
-struct AxisTable {              // per (image, axis); weights k-major so that neighbouring columns read neighbouring words
-    int base[OUT];              // first source index of output index o
-    int cnt[OUT];               // number of taps (0: the record is invalid, the output is 0)
-    float w[KMAX][OUT];
-};
+using AxisTable = AxisTableT<KMAX>;
 constexpr size_t kTableBytes = sizeof(AxisTable);
 constexpr size_t kPrerotBytes = (size_t)OUT * OUT * 3 * sizeof(float);
 static_assert(kTableBytes % 16 == 0 && kPrerotBytes % 16 == 0, "workspace sections stay 16-byte aligned");
@@ -41,70 +34,6 @@ __device__ inline bool record_ok(const clibd_image_xform& x, size_t data_bytes) 
     if (x.H0 > DOWN_MAX * x.H1 || x.W0 > DOWN_MAX * x.W1 || x.offset < 0) return false;
     const size_t n = (size_t)x.H0 * (size_t)x.W0 * 3;
     return (size_t)x.offset <= data_bytes && n <= data_bytes - (size_t)x.offset;
-}
-
-// torch's antialiased bilinear taps of output index o for in -> out (aten UpSampleKernel _compute_indices_min_size_weights_aa):
-// scale = in/out, center = scale (o + 0.5), support = max(scale, 1), taps [max(int(center - support + 0.5), 0),
-// min(int(center + support + 0.5), in)), weight max(0, 1 - |(t - center + 0.5) / max(scale, 1)|), normalised to sum 1.
-struct Taps {
-    int lo, hi;
-    float center, inv, total;
-    __device__ float raw(int t) const { return fmaxf(0.f, 1.f - fabsf(((float)t - center + 0.5f) * inv)); }
-    __device__ float weight(int t) const { return raw(t) / total; }
-};
-
-__device__ inline Taps taps_of(int o, int in, int out) {
-    Taps T;
-    const float scale = (float)in / (float)out;
-    const float support = scale >= 1.f ? scale : 1.f;
-    T.center = (float)((double)scale * ((double)o + 0.5));
-    T.inv = scale >= 1.f ? 1.f / scale : 1.f;
-    T.lo = max((int)((double)T.center - (double)support + 0.5), 0);
-    T.hi = min((int)((double)T.center + (double)support + 0.5), in);
-    T.total = 0.f;
-    for (int t = T.lo; t < T.hi; ++t) T.total += T.raw(t);
-    if (T.total == 0.f) T.total = 1.f;
-    return T;
-}
-
-// Composite weights of output index o on one axis: crop resample ext -> 224 (taps clamped to [0, ext), offset by off into the resized
-// axis of size mid), then the resize in -> mid.  Sizes that do not change are exact copies (torch's filter at unit scale).
-__device__ void axis_weights(int o, int in, int mid, int off, int ext, bool ok, AxisTable* __restrict__ T) {
-    if (!ok) {
-        T->base[o] = 0;
-        T->cnt[o] = 0;
-        return;
-    }
-    const bool crop_copy = ext == OUT, resize_copy = in == mid;
-    Taps C;
-    if (crop_copy) {
-        C.lo = o; C.hi = o + 1; C.center = 0.f; C.inv = 1.f; C.total = 1.f;
-    } else {
-        C = taps_of(o, ext, OUT);
-    }
-    int lo, hi;
-    if (resize_copy) {
-        lo = off + C.lo;
-        hi = off + C.hi;
-    } else {
-        lo = taps_of(off + C.lo, in, mid).lo;
-        hi = taps_of(off + C.hi - 1, in, mid).hi;
-    }
-    const int n = min(max(hi - lo, 0), KMAX);
-    for (int k = 0; k < n; ++k) T->w[k][o] = 0.f;
-    for (int c = C.lo; c < C.hi; ++c) {
-        const float wc = crop_copy ? 1.f : C.weight(c);
-        const int t = off + c;
-        if (resize_copy) {
-            if (t - lo < n) T->w[t - lo][o] += wc;
-        } else {
-            const Taps R = taps_of(t, in, mid);
-            for (int s = R.lo; s < R.hi; ++s)
-                if (s - lo >= 0 && s - lo < n) T->w[s - lo][o] += wc * R.weight(s);
-        }
-    }
-    T->base[o] = lo;
-    T->cnt[o] = n;
 }
 
 __global__ __launch_bounds__(256) void axis_weights_kernel(const clibd_image_xform* __restrict__ xf, size_t data_bytes,
@@ -127,52 +56,8 @@ __global__ __launch_bounds__(256) void resample_kernel(const unsigned char* __re
     const clibd_image_xform x = xf[b];
     const AxisTable* TV = tables + 2 * (size_t)b;
     const AxisTable* TH = TV + 1;
-    int S0 = 0x7fffffff, S1 = 0;          // source rows the band needs (empty for an invalid record: every cnt is 0)
-    for (int r = r0; r < r0 + RB; ++r) {
-        const int n = TV->cnt[r];
-        if (n > 0) {
-            S0 = min(S0, TV->base[r]);
-            S1 = max(S1, TV->base[r] + n);
-        }
-    }
-    const unsigned char* img = data + x.offset;
     float acc[IPT][3];
-#pragma unroll
-    for (int j = 0; j < IPT; ++j) acc[j][0] = acc[j][1] = acc[j][2] = 0.f;
-
-    for (int c0 = S0; c0 < S1; c0 += CAP) {
-        const int nrow = min(CAP, S1 - c0);
-        __syncthreads();                  // the previous chunk's readers are done
-        for (int i = tid; i < nrow * OUT; i += 256) {
-            const int rr = i / OUT, o = i - rr * OUT;
-            const int xb = TH->base[o], n = TH->cnt[o];
-            const unsigned char* p = img + ((size_t)(c0 + rr) * x.W0 + xb) * 3;
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-            for (int k = 0; k < n; ++k) {
-                const float w = TH->w[k][o];
-                a0 += w * (float)p[3 * k];
-                a1 += w * (float)p[3 * k + 1];
-                a2 += w * (float)p[3 * k + 2];
-            }
-            rows[rr][o * 3] = a0;
-            rows[rr][o * 3 + 1] = a1;
-            rows[rr][o * 3 + 2] = a2;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < IPT; ++j) {
-            const int i = tid + 256 * j;
-            const int rr = i / OUT, o = i - rr * OUT, r = r0 + rr;
-            const int vb = TV->base[r], vn = TV->cnt[r];
-            const int k0 = max(c0, vb), k1 = min(c0 + nrow, vb + vn);
-            for (int s = k0; s < k1; ++s) {
-                const float w = TV->w[s - vb][r];
-                acc[j][0] += w * rows[s - c0][o * 3];
-                acc[j][1] += w * rows[s - c0][o * 3 + 1];
-                acc[j][2] += w * rows[s - c0][o * 3 + 2];
-            }
-        }
-    }
+    resample_band(data + x.offset, x.W0, TV, TH, r0, tid, rows, acc);
     // pixel values are u8 / 255 (ToTensor, IEEE division); the weights act on the bytes, so an exact copy stays exact
     const bool rot = x.flags & CLIBD_XF_ROTATE, hf = x.flags & CLIBD_XF_HFLIP, vf = x.flags & CLIBD_XF_VFLIP;
 #pragma unroll

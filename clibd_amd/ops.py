@@ -933,6 +933,30 @@ def image_transform(data: torch.Tensor, xforms: torch.Tensor, workspace: Optiona
     return out
 
 
+def simclr_views(data: torch.Tensor, xforms: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Packed RGB HWC uint8 pixels `data` [N] + one record per view `xforms` int32 [n, 16] (struct clibd_view_xform; built by
+    clibd_amd.simclr_views) -> fp32 [n,3,224,224]: crop / flip / colour jitter / grayscale / blur of the SimCLR pipeline
+    (clibd_simclr_views_u8).  The records are validated on the host when they are built; a bad one yields a zero image and the
+    kernels read no byte outside `data` whatever the records hold.  workspace: a uint8 device buffer to reuse (grown when short)."""
+    _chk(data, torch.uint8, "data")
+    _chk(xforms, I32, "xforms")
+    if data.dim() != 1 or data.numel() == 0:
+        raise ValueError("simclr_views: data must be a non-empty 1-D uint8 tensor")
+    if xforms.dim() != 2 or xforms.shape[1] != 16 or xforms.shape[0] == 0 or xforms.device != data.device:
+        raise ValueError("simclr_views: xforms must be int32 [n, 16] on the data's device")
+    n = xforms.shape[0]
+    lib = _lib.load()
+    need = int(lib.clibd_simclr_views_workspace_bytes(n))
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace("simclr_views", need, data.device)
+    else:
+        _chk(workspace, torch.uint8, "workspace")
+    out = torch.empty((n, 3, 224, 224), dtype=F32, device=data.device)
+    check(lib.clibd_simclr_views_u8(data.data_ptr(), data.numel(), xforms.data_ptr(), n, out.data_ptr(), workspace.data_ptr(),
+                                    workspace.numel(), _stream()), "simclr_views_u8")
+    return out
+
+
 def topk_label_hits(idx: torch.Tensor, key_labels: torch.Tensor, query_labels: torch.Tensor, class_offset, k_list, segment: Optional[torch.Tensor] = None,
                     nseg: int = 1):
     """clibd_topk_label_hits: score a finished search against per-level class ids.  idx int64 [Q, kmax] (a search's output),

@@ -8,8 +8,9 @@ DDP-wrapped model, so files travel in both directions.
 The ViT runs through `clibd_amd.towers.ViTTower` under full fine-tuning (bf16 GEMM operands, fp32 accumulation, statistics and
 master weights: there is no fp16 GradScaler path, no wandb and no tensorboard); the loss is the fused NT-Xent kernel
 (csrc/ntxent.hip, no N x N matrix in memory) and the optimizer `clibd_amd.optim.FusedAdam` (torch.optim.Adam with coupled L2).
-The view augmentations of the reference's data pipeline (colour jitter, grayscale, blur) are not part of this module: a step takes
-the two view tensors, as the contrastive step takes images.
+A step takes the two view tensors, as the contrastive step takes images, or a packed batch of decoded pixels with one record per
+view (`clibd_amd.simclr_views.pack_two_views` / `collate_two_views`): the view augmentations of the reference's data pipeline (crop,
+flip, colour jitter, grayscale, blur) then run on the device (csrc/views.hip) and feed the tower directly.
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, simclr_views
 from .engine import NotSupportedYet
 from .model.image_encoder import create_vit
 from .model.simple_clip import SimpleCLIP, _get
@@ -180,9 +181,16 @@ class SimCLR(object):
         matrix with the positive moved to column 0 — is never formed.  `self.criterion.last_top1` holds the top-1 hit count."""
         return self.criterion(features)
 
-    def train_step(self, images_1, images_2):
-        """cat -> forward -> NT-Xent -> backward -> optimizer step; returns the device loss.  No host synchronisation."""
-        images = torch.cat([images_1, images_2], dim=0).to(self.device)
+    def train_step(self, images_1, images_2=None):
+        """cat -> forward -> NT-Xent -> backward -> optimizer step; returns the device loss.  No host synchronisation.
+        `images_1` alone may be a packed batch (`simclr_views.pack_two_views`): its 2b views are generated on the device, first views
+        then second views, and there is no cat."""
+        if simclr_views.is_packed(images_1):
+            if images_2 is not None:
+                raise ValueError("SimCLR.train_step: a packed batch holds both views")
+            images = simclr_views.apply(images_1, self.device)
+        else:
+            images = torch.cat([images_1, images_2], dim=0).to(self.device)
         self.optimizer.zero_grad()
         features = self.model(images)
         loss = self.info_nce_loss(features)
@@ -202,11 +210,16 @@ class SimCLR(object):
             running = torch.zeros((), dtype=F32, device=self.device)
             hits = torch.zeros((), dtype=torch.int64, device=self.device)
             n = rows = 0
-            for images_1, images_2 in train_loader:
-                running += self.train_step(images_1, images_2)
+            for batch in train_loader:           # (images_1, images_2), or a packed batch of both views
+                if simclr_views.is_packed(batch):
+                    running += self.train_step(batch)
+                    rows += batch["xforms"].shape[0]
+                else:
+                    images_1, images_2 = batch
+                    running += self.train_step(images_1, images_2)
+                    rows += 2 * images_1.shape[0]
                 hits += self.criterion.last_top1[0]
                 n += 1
-                rows += 2 * images_1.shape[0]
             epoch_loss_avg, nhits = torch.stack([running / max(n, 1), hits.to(F32)]).tolist()   # the one host fetch of the epoch
             top1 = 100.0 * nhits / max(rows, 1)
             # warmup for the first epochs (reference util/simclr.py:144-146)
