@@ -146,6 +146,17 @@ VIEW_SIGNATURES = {
     "clibd_simclr_views_u8": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# the linear-probe classifier (include/clibd_hip_classifier.h): a fourth additive table, bound after the other three
+CLS_SIGNATURES = {
+    "clibd_linear_f32_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "clibd_linear_f32_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "clibd_linear_f32_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_ce_rows_workspace_bytes": (c_size_t, [c_int]),
+    "clibd_ce_rows_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_ce_rows_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "clibd_softmax_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -169,7 +180,7 @@ def load() -> C.CDLL:
             "clibd_amd has no CPU fallback for its compute path."
         )
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

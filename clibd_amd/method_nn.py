@@ -207,6 +207,45 @@ def _prepared(keys, dev):
     return (E.prepare_key_bank(k) if eligible else k), Nk
 
 
+def seen_unseen_from_sources(conf, idx_a, idx_b, labels_a, labels_b, seen_gt, unseen_gt, ks, searched_threshold, grid, with_predictions=True):
+    """What follows the two sources of a seen/unseen method, shared by method_nn (A: the seen-key search) and method_linear (A: the
+    classifier): conf fp32 [Q, m] and idx_a int64 [Q, m] index `labels_a`, idx_b int64 [Q, m] indexes `labels_b`, the Q queries are the
+    seen split followed by the unseen one.  The threshold sweep over `grid` (skipped when `searched_threshold` is given), the merge at
+    the chosen threshold and ONE clibd_topk_label_hits launch on the merged indices; returns the reference's two output dicts."""
+    dev = conf.device
+    Qs, Qu = len(seen_gt), len(unseen_gt)
+    Nka, Nkb = len(labels_a), len(labels_b)
+    codec = LabelCodec()                                   # one codec: ids agree across the two key sets and the queries
+    ids_a, ids_b = codec.encode(labels_a), codec.encode(labels_b)
+    s_ids, u_ids = codec.encode(seen_gt), codec.encode(unseen_gt)
+    table_a, table_b = torch.from_numpy(ids_a).to(dev), torch.from_numpy(ids_b).to(dev)
+    q_ids = torch.from_numpy(np.concatenate([s_ids, u_ids])).to(dev)
+    segment = torch.from_numpy(np.repeat(np.array([0, 1], dtype=np.int32), [Qs, Qu])).to(dev)
+    if searched_threshold is None:
+        hits = ops.threshold_sweep_hits(conf, idx_a, idx_b, table_a, table_b, q_ids, torch.from_numpy(np.ascontiguousarray(grid)).to(dev), [1],
+                                        segment=segment, nseg=2).cpu().numpy()[:, :, 0, SPECIES]
+        best = choose_threshold(hits, [Qs, Qu], grid)
+    else:
+        best = searched_threshold
+    merged, _ = ops.threshold_merge(conf, idx_a, idx_b, Nka, Nkb, float(best))
+    off = codec.class_offset()
+    _, lh, ch, cc = ops.topk_label_hits(merged, torch.cat([table_a, table_b]), q_ids, off, ks, segment=segment, nseg=2)
+    lh, ch, cc = lh.cpu().numpy(), ch.cpu().numpy(), cc.cpu().numpy()
+    rows = list(range(len(ks)))
+    merged_h = merged.cpu().numpy()
+    if with_predictions:
+        preds = codec.decode_rows(np.concatenate([ids_a, ids_b]), merged_h)
+        preds = (preds[:Qs], preds[Qs:])
+    else:
+        preds = (merged_h[:Qs], merged_h[Qs:])
+    out = []
+    for s, (ids, gt) in enumerate(((s_ids, seen_gt), (u_ids, unseen_gt))):
+        micro, macro, per_class = E._split_accuracy(lh[s], ch[s], cc[s], ids, codec, off, ks, rows)
+        out.append({"final_pred_labels": preds[s], "gt_labels": gt, "best_threshold": best, "micro_acc": micro, "macro_acc": macro,
+                    "per_class_acc": per_class})
+    return out[0], out[1]
+
+
 def seen_unseen_from_features(seen_query, unseen_query, seen_keys, seen_keys_label, unseen_keys, unseen_keys_label, seen_gt, unseen_gt, k_list,
                               searched_threshold=None, thresholds=None, with_predictions=True, num_intervals=1000, max_k=5):
     """method_1_inference_and_eval_for_seen_and_unseen from features (device tensors, numpy arrays, or prepared `KeyBank`s for the keys):
@@ -233,36 +272,9 @@ def seen_unseen_from_features(seen_query, unseen_query, seen_keys, seen_keys_lab
         raise ValueError(f"method_nn: one label per key, and at least {m} keys per key set")
     conf, idx_a = E.topk_search(queries, bank_a, m, cache=False)
     _, idx_b = E.topk_search(queries, bank_b, m, cache=False)
-    codec = LabelCodec()                                   # one codec: ids agree across the two key sets and the queries
-    ids_a, ids_b = codec.encode(seen_keys_label), codec.encode(unseen_keys_label)
-    s_ids, u_ids = codec.encode(seen_gt), codec.encode(unseen_gt)
-    table_a, table_b = torch.from_numpy(ids_a).to(dev), torch.from_numpy(ids_b).to(dev)
-    q_ids = torch.from_numpy(np.concatenate([s_ids, u_ids])).to(dev)
-    segment = torch.from_numpy(np.repeat(np.array([0, 1], dtype=np.int32), [Qs, Qu])).to(dev)
-    if searched_threshold is None:
-        grid = _grid(num_intervals, thresholds)
-        hits = ops.threshold_sweep_hits(conf, idx_a, idx_b, table_a, table_b, q_ids, torch.from_numpy(np.ascontiguousarray(grid)).to(dev), [1],
-                                        segment=segment, nseg=2).cpu().numpy()[:, :, 0, SPECIES]
-        best = choose_threshold(hits, [Qs, Qu], grid)
-    else:
-        best = searched_threshold
-    merged, _ = ops.threshold_merge(conf, idx_a, idx_b, Nka, Nkb, float(best))
-    off = codec.class_offset()
-    _, lh, ch, cc = ops.topk_label_hits(merged, torch.cat([table_a, table_b]), q_ids, off, ks, segment=segment, nseg=2)
-    lh, ch, cc = lh.cpu().numpy(), ch.cpu().numpy(), cc.cpu().numpy()
-    rows = list(range(len(ks)))
-    merged_h = merged.cpu().numpy()
-    if with_predictions:
-        preds = codec.decode_rows(np.concatenate([ids_a, ids_b]), merged_h)
-        preds = (preds[:Qs], preds[Qs:])
-    else:
-        preds = (merged_h[:Qs], merged_h[Qs:])
-    out = []
-    for s, (ids, gt) in enumerate(((s_ids, seen_gt), (u_ids, unseen_gt))):
-        micro, macro, per_class = E._split_accuracy(lh[s], ch[s], cc[s], ids, codec, off, ks, rows)
-        out.append({"final_pred_labels": preds[s], "gt_labels": gt, "best_threshold": best, "micro_acc": micro, "macro_acc": macro,
-                    "per_class_acc": per_class})
-    return out[0], out[1]
+    grid = _grid(num_intervals, thresholds) if searched_threshold is None else None
+    return seen_unseen_from_sources(conf, idx_a, idx_b, seen_keys_label, unseen_keys_label, seen_gt, unseen_gt, ks, searched_threshold, grid,
+                                    with_predictions)
 
 
 def inference_with_original_image_encoder_and_dna_encoder(original_model, seen_query_dataloader, unseen_query_dataloader, key_dataloaders, device,

@@ -1,4 +1,4 @@
-"""Tensor-level wrappers over the C ABI (include/clibd_hip.h).
+"""Tensor-level wrappers over the C ABI (include/clibd_hip.h and the additive headers beside it).
 
 PyTorch is plumbing here: it owns device memory and the HIP stream; every function below only checks the
 operands on the host, takes raw pointers and enqueues hand-written gfx950 kernels on torch's current stream.
@@ -1206,3 +1206,125 @@ def gemm_nt_splitk(a: torch.Tensor, w: torch.Tensor, out_f32: torch.Tensor, accu
         return False    # declined before anything was enqueued: the caller uses gemm_nt(split_k=)
     check(rc, "gemm_bf16_nt_splitk")
     return True
+
+
+# ------------------------------------------------------------------------------------------------ linear-probe classifier (include/clibd_hip_classifier.h)
+def _linear_f32_ws(B: int, Ccls: int, D: int, device) -> torch.Tensor:
+    return _workspace("linear_f32", int(_lib.load().clibd_linear_f32_workspace_bytes(B, Ccls, D)), device)
+
+
+def linear_f32_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x w^T + bias at split-bf16 accuracy (clibd_linear_f32_fwd): x fp32 [B, D], w fp32 [C, D], bias fp32 [C] or None -> fp32 [B, C]
+    (`out`: a 2-D fp32 tensor with unit inner stride to write into)."""
+    _chk(x, F32, "x"); _chk(w, F32, "w")
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1]:
+        raise ValueError("linear_f32_fwd: expected x [B, D] and w [C, D]")
+    B, D = x.shape
+    Ccls = w.shape[0]
+    if bias is not None:
+        _chk(bias, F32, "bias")
+        if bias.numel() != Ccls:
+            raise ValueError("linear_f32_fwd: bias must have C elements")
+    if out is None:
+        out = torch.empty((B, Ccls), dtype=F32, device=x.device)
+    else:
+        _chk(out, F32, "out", contiguous=False)
+        if tuple(out.shape) != (B, Ccls):
+            raise ValueError(f"linear_f32_fwd: out must be [{B}, {Ccls}]")
+    ws = _linear_f32_ws(B, Ccls, D, x.device)
+    check(_lib.load().clibd_linear_f32_fwd(x.data_ptr(), w.data_ptr(), _p(bias), B, Ccls, D, out.data_ptr(), _rowmajor(out, "out"), ws.data_ptr(),
+                                           ws.numel(), _stream()), "linear_f32_fwd")
+    return out
+
+
+def linear_f32_bwd(dout: torch.Tensor, x: torch.Tensor, w: torch.Tensor, need_dx: bool = True, need_dw: bool = True, need_db: bool = True):
+    """(dx [B, D] = dout w, dw [C, D] = dout^T x, db [C] = dout.sum(0)) through the split images (clibd_linear_f32_bwd); an output that is
+    not needed is None.  Fixed summation orders: two calls give the same bits."""
+    _chk(dout, F32, "dout"); _chk(x, F32, "x"); _chk(w, F32, "w")
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1] or tuple(dout.shape) != (x.shape[0], w.shape[0]):
+        raise ValueError("linear_f32_bwd: expected dout [B, C], x [B, D] and w [C, D]")
+    B, D = x.shape
+    Ccls = w.shape[0]
+    dev = x.device
+    dx = torch.empty((B, D), dtype=F32, device=dev) if need_dx else None
+    dw = torch.empty((Ccls, D), dtype=F32, device=dev) if need_dw else None
+    db = torch.empty((Ccls,), dtype=F32, device=dev) if need_db else None
+    ws = _linear_f32_ws(B, Ccls, D, dev)
+    check(_lib.load().clibd_linear_f32_bwd(dout.data_ptr(), x.data_ptr(), w.data_ptr(), B, Ccls, D, _p(dx), _p(dw), _p(db), ws.data_ptr(), ws.numel(),
+                                           _stream()), "linear_f32_bwd")
+    return dx, dw, db
+
+
+_ce_err: dict = {}   # device -> the int32 error word of ce_rows_fwd (sticky: bit 0 = a target outside [0, C))
+
+
+def ce_error_word(device) -> torch.Tensor:
+    """The device word that ce_rows_fwd ORs its target-range flag into.  Reading it is a host synchronisation, so nothing on the
+    training path does; `ce_rows_fwd(check=True)` and a caller at an epoch's end may."""
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    e = _ce_err.get(dev)
+    if e is None:
+        e = _ce_err[dev] = torch.zeros((1,), dtype=I32, device=dev)
+    return e
+
+
+def ce_rows_fwd(logits: torch.Tensor, target: torch.Tensor, check: bool = False):   # `check` shadows _lib.check here: the calls below name the module
+    """nn.CrossEntropyLoss() forward (mean over rows, integer targets; clibd_ce_rows_fwd): logits fp32 [B, C] with unit inner stride,
+    target int64 [B] -> (loss fp32 [1], lse fp32 [B]) on the device.  A target outside [0, C) contributes nothing and sets bit 0 of
+    `ce_error_word`; with check=True the word is read back (a host sync), cleared, and such a target raises ValueError."""
+    _chk(logits, F32, "logits", contiguous=False); _chk(target, I64, "target")
+    ld = _rowmajor(logits, "logits")
+    B, Ccls = logits.shape
+    if tuple(target.shape) != (B,):
+        raise ValueError(f"ce_rows_fwd: target must be [{B}]")
+    dev = logits.device
+    loss = torch.empty((1,), dtype=F32, device=dev)
+    lse = torch.empty((B,), dtype=F32, device=dev)
+    err = ce_error_word(dev)
+    lib = _lib.load()
+    ws = _workspace("ce_rows", int(lib.clibd_ce_rows_workspace_bytes(B)), dev)
+    _lib.check(lib.clibd_ce_rows_fwd(logits.data_ptr(), ld, target.data_ptr(), B, Ccls, lse.data_ptr(), loss.data_ptr(), err.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), _stream()), "ce_rows_fwd")
+    if check:
+        e = int(err.item())
+        err.zero_()
+        if e & 1:
+            raise ValueError(f"ce_rows_fwd: a target outside [0, {Ccls})")
+    return loss, lse
+
+
+def ce_rows_bwd(logits: torch.Tensor, target: torch.Tensor, lse: torch.Tensor, dloss: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d loss / d logits [B, C] = dloss / B * (softmax - onehot) (clibd_ce_rows_bwd); dloss: a 1-element fp32 device tensor or None (1).
+    Rows whose target lies outside [0, C) are zero."""
+    _chk(logits, F32, "logits", contiguous=False); _chk(target, I64, "target"); _chk(lse, F32, "lse")
+    ld = _rowmajor(logits, "logits")
+    B, Ccls = logits.shape
+    if tuple(target.shape) != (B,) or lse.numel() != B:
+        raise ValueError(f"ce_rows_bwd: target and lse must be [{B}]")
+    if dloss is not None:
+        _chk(dloss, F32, "dloss")
+        if dloss.numel() != 1:
+            raise ValueError("ce_rows_bwd: dloss must have one element")
+    d = torch.empty((B, Ccls), dtype=F32, device=logits.device)
+    _lib.check(_lib.load().clibd_ce_rows_bwd(logits.data_ptr(), ld, target.data_ptr(), lse.data_ptr(), B, Ccls, _p(dloss), d.data_ptr(), Ccls, _stream()),
+               "ce_rows_bwd")
+    return d
+
+
+def softmax_topk(logits: torch.Tensor, k: int = 5):
+    """torch.topk(F.softmax(logits, -1), k, sorted=True) (clibd_softmax_topk): (conf fp32 [B, k], idx int64 [B, k]); equal values resolve
+    to the lower index.  1 <= k <= 8, and k > C raises as in torch."""
+    _chk(logits, F32, "logits", contiguous=False)
+    ld = _rowmajor(logits, "logits")
+    B, Ccls = logits.shape
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("softmax_topk: k must be in 1..8")
+    if k > Ccls:
+        raise RuntimeError("softmax_topk: selected index k out of range")
+    conf = torch.empty((B, k), dtype=F32, device=logits.device)
+    idx = torch.empty((B, k), dtype=I64, device=logits.device)
+    _lib.check(_lib.load().clibd_softmax_topk(logits.data_ptr(), ld, B, Ccls, k, conf.data_ptr(), idx.data_ptr(), _stream()), "softmax_topk")
+    return conf, idx
