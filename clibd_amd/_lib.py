@@ -157,6 +157,15 @@ CLS_SIGNATURES = {
     "clibd_softmax_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
+# the embedding analysis (include/clibd_hip_analysis.h): a fifth additive table, bound after the other four
+ANALYSIS_SIGNATURES = {
+    "clibd_silhouette_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_silhouette_samples": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_same_label_nearest": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+    "clibd_confusion_counts": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -180,7 +189,8 @@ def load() -> C.CDLL:
             "clibd_amd has no CPU fallback for its compute path."
         )
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items())
+                              + list(ANALYSIS_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1328,3 +1328,78 @@ def softmax_topk(logits: torch.Tensor, k: int = 5):
     idx = torch.empty((B, k), dtype=I64, device=logits.device)
     _lib.check(_lib.load().clibd_softmax_topk(logits.data_ptr(), ld, B, Ccls, k, conf.data_ptr(), idx.data_ptr(), _stream()), "softmax_topk")
     return conf, idx
+
+
+# ---- the embedding analysis (include/clibd_hip_analysis.h) ----------------------------------------------------------------------------
+def _host_seg(seg, name: str):
+    """run offsets as (host int32 array, C): the C entries validate the host copy before they launch; the caller uploads the device copy"""
+    import numpy as np
+
+    host = np.ascontiguousarray(seg.detach().cpu().numpy() if torch.is_tensor(seg) else np.asarray(seg), dtype=np.int32)
+    if host.ndim != 1 or host.size < 2:
+        raise ValueError(f"{name}: seg must be a 1-D array of C + 1 run offsets")
+    return host, host.size - 1
+
+
+def silhouette_workspace_bytes(N: int, col_chunk: int = 0) -> int:
+    return int(_lib.load().clibd_silhouette_workspace_bytes(int(N), int(col_chunk)))
+
+
+def silhouette_samples(x: torch.Tensor, seg, col_chunk: int = 0) -> torch.Tensor:
+    """sklearn's silhouette_samples(x, labels) for rows already ordered by cluster (clibd_silhouette_samples): x fp32 [N, D], D a multiple
+    of 32; seg [C + 1] the run offsets (host array or tensor); returns s fp32 [N] in the order of x's rows.  Fewer than 2 or more than
+    N - 1 clusters raises ValueError with sklearn's condition."""
+    _chk(x, F32, "x")
+    if x.dim() != 2:
+        raise ValueError("silhouette_samples: x must be [N, D]")
+    N, D = x.shape
+    host, Ccl = _host_seg(seg, "silhouette_samples")
+    if not 2 <= Ccl <= N - 1:
+        raise ValueError(f"Number of labels is {Ccl}. Valid values are 2 to n_samples - 1 (inclusive)")
+    if D % 32 != 0:
+        raise ValueError("silhouette_samples: D must be a multiple of 32 (zero pad the columns)")
+    seg_d = torch.from_numpy(host).to(x.device)
+    need = silhouette_workspace_bytes(N, col_chunk)
+    if need == 0:
+        raise ValueError("silhouette_samples: col_chunk must be 0 or a positive multiple of 64 and N at most 2^24")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    out = torch.empty(N, dtype=F32, device=x.device)
+    check(_lib.load().clibd_silhouette_samples(x.data_ptr(), N, D, seg_d.data_ptr(), host.ctypes.data, Ccl, int(col_chunk), out.data_ptr(),
+                                               ws.data_ptr(), need, _stream()), "silhouette_samples")
+    return out
+
+
+def same_label_nearest(q: torch.Tensor, k: torch.Tensor, seg, qclass: torch.Tensor):
+    """The distance from each query to the nearest key of its own class (clibd_same_label_nearest): q fp32 [Nq, D], k fp32 [Nk, D] grouped by
+    class with run offsets seg [C + 1], qclass int32 [Nq] in [0, C) or -1.  Returns (dist fp32 [Nq], arg int32 [Nq]); the lowest key row
+    wins a tie; an empty class or -1 gives (+inf, -1)."""
+    _chk(q, F32, "q", contiguous=False)
+    _chk(k, F32, "k", contiguous=False)
+    _chk(qclass, I32, "qclass")
+    ldq, ldk = _rowmajor(q, "q"), _rowmajor(k, "k")
+    if q.shape[1] != k.shape[1]:
+        raise ValueError("same_label_nearest: q and k differ in width")
+    Nq, D = q.shape
+    Nk = k.shape[0]
+    if qclass.shape != (Nq,):
+        raise ValueError("same_label_nearest: qclass must be [Nq]")
+    host, Ccl = _host_seg(seg, "same_label_nearest")
+    seg_d = torch.from_numpy(host).to(q.device)
+    dist = torch.empty(Nq, dtype=F32, device=q.device)
+    arg = torch.empty(Nq, dtype=I32, device=q.device)
+    check(_lib.load().clibd_same_label_nearest(q.data_ptr(), ldq, k.data_ptr(), ldk, Nq, Nk, D, seg_d.data_ptr(), host.ctypes.data, Ccl,
+                                               qclass.data_ptr(), dist.data_ptr(), arg.data_ptr(), _stream()), "same_label_nearest")
+    return dist, arg
+
+
+def confusion_counts(true_code: torch.Tensor, pred_code: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """int32 [C, C] counts, rows = true (clibd_confusion_counts); a sample whose true or predicted code is -1 is skipped."""
+    _chk(true_code, I32, "true_code")
+    _chk(pred_code, I32, "pred_code")
+    if true_code.dim() != 1 or true_code.shape != pred_code.shape:
+        raise ValueError("confusion_counts: true_code and pred_code must be 1-D and of equal length")
+    Ccl = int(num_classes)
+    out = torch.empty((Ccl, Ccl), dtype=I32, device=true_code.device)
+    check(_lib.load().clibd_confusion_counts(true_code.data_ptr(), pred_code.data_ptr(), true_code.numel(), Ccl, out.data_ptr(), _stream()),
+          "confusion_counts")
+    return out
