@@ -166,6 +166,14 @@ ANALYSIS_SIGNATURES = {
     "clibd_confusion_counts": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
 }
 
+# the attention rollout (include/clibd_hip_rollout.h): a sixth additive table, bound after the other five
+ROLLOUT_SIGNATURES = {
+    "clibd_attn_fused_maps": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "clibd_rollout_discard_workspace_bytes": (c_size_t, [c_int]),
+    "clibd_rollout_discard": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "clibd_rollout_chain": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -190,7 +198,7 @@ def load() -> C.CDLL:
         )
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items())
-                              + list(ANALYSIS_SIGNATURES.items())):
+                              + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

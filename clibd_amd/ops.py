@@ -1403,3 +1403,64 @@ def confusion_counts(true_code: torch.Tensor, pred_code: torch.Tensor, num_class
     check(_lib.load().clibd_confusion_counts(true_code.data_ptr(), pred_code.data_ptr(), true_code.numel(), Ccl, out.data_ptr(), _stream()),
           "confusion_counts")
     return out
+
+
+# ---- the attention rollout (include/clibd_hip_rollout.h) --------------------------------------------------------------------------------
+FUSE_MEAN, FUSE_MAX, FUSE_MIN = 0, 1, 2
+
+
+def rollout_ld(S: int) -> int:
+    """the row stride of a fused map: S rounded up to 4, so that a row takes 16-byte stores"""
+    return (int(S) + 3) // 4 * 4
+
+
+def attn_fused_maps(qkv: torch.Tensor, B: int, S: int, heads: int, fusion: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fuse_h softmax(q_h k_h^T / 8) of one layer (clibd_attn_fused_maps): qkv bf16 [B * S, 3 * 64 * heads] as clibd_attention_fwd reads it;
+    returns (or fills) fp32 [B, S, rollout_ld(S)], whose columns >= S are padding."""
+    _chk(qkv, BF16, "qkv")
+    B, S, heads = int(B), int(S), int(heads)
+    if qkv.dim() != 2 or tuple(qkv.shape) != (B * S, 3 * 64 * heads):
+        raise ValueError(f"attn_fused_maps: qkv must be [{B * S}, {3 * 64 * heads}] (head dim 64)")
+    if fusion not in (FUSE_MEAN, FUSE_MAX, FUSE_MIN):
+        raise ValueError("attn_fused_maps: fusion must be FUSE_MEAN, FUSE_MAX or FUSE_MIN")
+    ld = rollout_ld(S)
+    if out is None:
+        out = torch.empty((B, S, ld), dtype=F32, device=qkv.device)
+    _chk(out, F32, "out")
+    if tuple(out.shape) != (B, S, ld):
+        raise ValueError(f"attn_fused_maps: out must be [{B}, {S}, {ld}]")
+    check(_lib.load().clibd_attn_fused_maps(qkv.data_ptr(), B, S, heads, int(fusion), out.data_ptr(), ld, _stream()), "attn_fused_maps")
+    return out
+
+
+def rollout_discard_(maps: torch.Tensor, S: int, k: int) -> torch.Tensor:
+    """In place on maps fp32 [..., S, ld] (clibd_rollout_discard): per map the k smallest of its S * S entries become 0, except entry [0, 0],
+    which still counts among the k; ties at the k-th value go in ascending flat index.  Returns the selection record, int64 [n, 4]: the bits of
+    the k-th smallest value, the entries below it, the entries equal to it that were taken, k."""
+    _chk(maps, F32, "maps")
+    S, k = int(S), int(k)
+    if maps.dim() < 2 or maps.shape[-2] != S or maps.shape[-1] < S:
+        raise ValueError("rollout_discard_: maps must be [..., S, ld] with ld >= S")
+    if not 0 <= k <= S * S:
+        raise ValueError("rollout_discard_: k must be in 0..S*S")
+    ld = maps.shape[-1]
+    n = maps.numel() // (S * ld)
+    need = int(_lib.load().clibd_rollout_discard_workspace_bytes(n))
+    ws = torch.empty(need // 4, dtype=I32, device=maps.device)
+    check(_lib.load().clibd_rollout_discard(maps.data_ptr(), n, S, ld, k, ws.data_ptr(), need, _stream()), "rollout_discard")
+    return ws.view(n, 4).to(I64) & 0xFFFFFFFF
+
+
+def rollout_chain(maps: torch.Tensor, S: int) -> torch.Tensor:
+    """The chain of the discarded maps (clibd_rollout_chain): maps fp32 [L, B, S, ld] in the order of application; returns fp32 [B, S - 1],
+    row 0 of the product of the column-normalised (F + I) / 2 without its first entry, divided by its maximum."""
+    _chk(maps, F32, "maps")
+    S = int(S)
+    if maps.dim() != 4 or maps.shape[2] != S or maps.shape[3] < S:
+        raise ValueError("rollout_chain: maps must be [L, B, S, ld] with ld >= S")
+    if S < 2:
+        raise ValueError("rollout_chain: S must be at least 2")
+    L, B, _, ld = maps.shape
+    out = torch.empty((B, S - 1), dtype=F32, device=maps.device)
+    check(_lib.load().clibd_rollout_chain(maps.data_ptr(), L, B, S, ld, out.data_ptr(), _stream()), "rollout_chain")
+    return out
