@@ -21,7 +21,7 @@ INCLUDE = HERE.parent / "include"
 LIB = HERE / "libclibd_hip.so"
 OBJ = CSRC / "build"
 ARCH = "gfx950"
-SOURCES = ["capi", "gemm", "gemm256", "gemm256_tn", "layernorm", "attention", "lora", "elementwise", "loss", "topk", "paramgrad", "evalacc", "augment", "ntxent", "views", "classifier", "analysis", "rollout"]
+SOURCES = ["capi", "gemm", "gemm256", "gemm256_tn", "layernorm", "attention", "lora", "elementwise", "loss", "topk", "paramgrad", "evalacc", "augment", "ntxent", "views", "split3", "classifier", "analysis", "rollout"]
 
 
 def _public_headers() -> list[Path]:

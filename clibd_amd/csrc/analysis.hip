@@ -299,17 +299,11 @@ static int sil_nchunk(int N, int cc) { return (int)(((long long)N + cc - 1) / cc
 
 static SilWs sil_carve(void* base, int N, int cc) {
     SilWs w;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = p ? p + off : nullptr;
-        off += (bytes + 255) / 256 * 256;
-        return q;
-    };
-    w.cid = (int*)take((size_t)N * 4);
-    w.nrm = (float*)take((size_t)N * 4);
-    w.part = (float*)take((size_t)sil_nchunk(N, cc) * 4 * (size_t)N * 4);
-    w.total = off;
+    Carver c(base);
+    w.cid = c.take<int>(N);
+    w.nrm = c.take<float>(N);
+    w.part = c.take<float>((size_t)sil_nchunk(N, cc) * 4 * (size_t)N);
+    w.total = c.total();
     return w;
 }
 

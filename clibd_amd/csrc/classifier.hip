@@ -6,7 +6,7 @@
 //   conf, idx = topk(softmax(logits), k)
 //
 // The confidences are compared with `>` against 1 001 thresholds and the class indices are scored under `==`, so the head does not
-// run at the towers' bf16 accuracy: the product uses the split-bf16 operands of K9 (loss.hip, split3.h) — x = hi + lo, w = hi + lo,
+// run at the towers' bf16 accuracy: the product is the split-bf16 module's (split3.hip, shared with K9) — x = hi + lo, w = hi + lo,
 // x w^T ~ hi·hi + hi·lo + lo·hi as ONE NT GEMM with K = 3D over [hi|hi|lo] and [hi|lo|hi] — and so do both backward products:
 //     dx = [Ghi | Ghi | Glo] . [Whi^T | Wlo^T | Whi^T]^T          dw = [Ghi^T | Glo^T | Ghi^T] . [Xhi^T | Xhi^T | Xlo^T]^T      (G = dout)
 // with every contraction zero padded to whole 64-wide K tiles.  Row statistics use one wave64 per row with the DPP / permlane
@@ -18,22 +18,6 @@
 #include "split3.h"
 
 namespace clibd {
-
-// the x-side image [hi | hi | lo] of in[R, C] (row stride ld_in), each segment zero padded to Cp columns: out [R, 3 Cp]
-__global__ __launch_bounds__(256) void split3_pad_kernel(const float* __restrict__ in, int ld_in, int R, int C, int Cp,
-                                                         unsigned short* __restrict__ out) {
-    const size_t total = (size_t)R * Cp;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = i / Cp;
-        const int c = (int)(i - r * Cp);
-        const float v = c < C ? in[r * (size_t)ld_in + c] : 0.f;
-        const unsigned short hi = f2bf(v);
-        unsigned short* o = out + r * 3 * (size_t)Cp;
-        o[c] = hi;
-        o[Cp + c] = hi;
-        o[2 * Cp + c] = f2bf(v - bf2f(hi));
-    }
-}
 
 // bias16[j] = bias[j] (j < C, bias given), 0 otherwise: the GEMM's epilogue reads all C16 columns
 __global__ __launch_bounds__(256) void pad_bias_kernel(const float* __restrict__ bias, int C, int C16, float* __restrict__ out) {
@@ -48,15 +32,6 @@ __global__ __launch_bounds__(256) void copy_cols_kernel(const float* __restrict_
         const size_t r = i / C;
         const int c = (int)(i - r * C);
         out[r * (size_t)ld_out + c] = S[r * (size_t)ldS + c];
-    }
-}
-
-__device__ __forceinline__ void online_add(float& m, float& s, float v) {
-    if (v > m) {
-        s = s * __expf(m - v) + 1.0f;
-        m = v;
-    } else {
-        s += __expf(v - m);
     }
 }
 
@@ -82,7 +57,7 @@ __global__ __launch_bounds__(256) void ce_rows_fwd_kernel(const float* __restric
         }
         j0 = nq << 2;
     }
-    for (int j = j0 + lane; j < C; j += 64) online_add(m, s, lr[j]);
+    for (int j = j0 + lane; j < C; j += 64) online_lse_add(m, s, lr[j]);
     const float mw = wave_max(m);
     s = wave_sum(s * __expf(m - mw));
     if (lane == 0) {
@@ -97,21 +72,6 @@ __global__ __launch_bounds__(256) void ce_rows_fwd_kernel(const float* __restric
         }
         row_loss[row] = term;
     }
-}
-
-// out[0] = (sum_i v[i]) / n, one workgroup, the summation order of loss.hip's reduce_rows_add_kernel (thread t takes i = t, t + 256, ...;
-// then an LDS tree)
-__global__ __launch_bounds__(256) void mean_rows_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
-    __shared__ float part[256];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) s += v[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = part[0] / (float)n;
 }
 
 // dlogits[i, j] = g / B * (exp(logit - lse_i) - [j == target_i]); a row with a bad target is zero
@@ -136,9 +96,6 @@ __global__ __launch_bounds__(256) void ce_rows_bwd_kernel(const float* __restric
 
 constexpr int TOPK_MAX = 8;
 
-// (a, ia) ranks before (b, ib): the larger value, equal values by the lower index
-__device__ __forceinline__ bool ranks_before(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
-
 // one wave per row.  Every lane keeps the 8 best (value, index) pairs of its stride-64 share in registers — the insertion is a fully
 // unrolled compare-exchange chain, so the slots stay named registers (no indexed local array, scratch 0) — together with the online max
 // and sum of the softmax.  Then k rounds: the wave's best head wins (wave_max of the values, then the lowest index among the lanes that
@@ -161,7 +118,7 @@ __global__ __launch_bounds__(256) void softmax_topk_kernel(const float* __restri
     }
     for (int j = lane; j < C; j += 64) {
         const float x = lr[j];
-        online_add(m, s, x);
+        online_lse_add(m, s, x);
         float cv = x;
         int ci = j;
         CLIBD_CEX(v0, i0) CLIBD_CEX(v1, i1) CLIBD_CEX(v2, i2) CLIBD_CEX(v3, i3)
@@ -186,67 +143,43 @@ __global__ __launch_bounds__(256) void softmax_topk_kernel(const float* __restri
 }
 
 struct ClsWs {
-    unsigned short *x3, *w3;   // [B,3D] = [hi|hi|lo],  [C16,3D] = [hi|lo|hi] (rows C.. zero)
-    float *bias16, *S;         // [C16],  [B,C16]: the GEMM's output block
-    unsigned short *G, *GT;    // dout: [B,3Cp] = [hi|hi|lo],  [C,3Bp] = [hi^T|lo^T|hi^T]
-    unsigned short *xT, *wT;   // [D,3Bp] = [hi^T|hi^T|lo^T],  [D,3Cp] = [hi^T|lo^T|hi^T]
-    float* bsum;               // clibd_batch_sum_f32's partials
+    Split3Ws p;           // x: [B,D] (M = B), y = w: [C,D] (N = C), g = dout
+    float *bias16, *S;    // [C16],  [B,C16]: the GEMM's output block
+    float* bsum;          // clibd_batch_sum_f32's partials
     size_t bsum_bytes, total;
 };
 
 static ClsWs carve(void* base, int B, int C, int D) {
     ClsWs w;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = p ? p + off : nullptr;
-        off += align_up(bytes, 256);
-        return q;
-    };
-    const int C16 = pad16(C), Cp = pad64(C), Bp = pad64(B);
-    w.x3 = (unsigned short*)take((size_t)B * 3 * D * 2);
-    w.w3 = (unsigned short*)take((size_t)C16 * 3 * D * 2);
-    w.bias16 = (float*)take((size_t)C16 * 4);
-    w.S = (float*)take((size_t)B * C16 * 4);
-    w.G = (unsigned short*)take((size_t)B * 3 * Cp * 2);
-    w.GT = (unsigned short*)take((size_t)C * 3 * Bp * 2);
-    w.xT = (unsigned short*)take((size_t)D * 3 * Bp * 2);
-    w.wT = (unsigned short*)take((size_t)D * 3 * Cp * 2);
+    Carver c(base);
+    w.p.carve(c, B, C, D);
+    w.bias16 = c.take<float>(pad16(C));
+    w.S = c.take<float>((size_t)B * pad16(C));
     w.bsum_bytes = clibd_batch_sum_workspace_bytes(B, (size_t)C);
-    w.bsum = (float*)take(w.bsum_bytes);
-    w.total = off;
+    w.bsum = (float*)c.take<char>(w.bsum_bytes);
+    w.total = c.total();
     return w;
 }
 
 constexpr int kMaxClasses = 1 << 24;   // class indices travel through fp32 in softmax_topk_kernel; nothing near it is in sight
 
 static int linear_check(const char* op, const float* x, const float* w, int B, int C, int D, const void* ws, size_t ws_bytes) {
-    char msg[kErrBufLen];
-    auto fail = [&](const char* what) {
-        snprintf(msg, sizeof msg, "%s: %s", op, what);
-        return set_error(CLIBD_EINVAL, msg);
-    };
-    if (!x || !w || !ws) return fail("null pointer");
-    if (B <= 0 || C <= 0 || D <= 0) return fail("non-positive shape");
-    if (C > kMaxClasses) return fail("C too large");
-    if (D % 64 != 0) return fail("D must be a multiple of 64");
-    if (!aligned16(x) || !aligned16(w)) return fail("x and w must be 16-byte aligned");
+    if (!x || !w || !ws) return fail(op, "null pointer");
+    if (B <= 0 || C <= 0 || D <= 0) return fail(op, "non-positive shape");
+    if (C > kMaxClasses) return fail(op, "C too large");
+    if (D % 64 != 0) return fail(op, "D must be a multiple of 64");
+    if (!aligned16(x) || !aligned16(w)) return fail(op, "x and w must be 16-byte aligned");
     if (!aligned16(ws) || ws_bytes < carve(nullptr, B, C, D).total)
-        return fail("workspace too small or misaligned (clibd_linear_f32_workspace_bytes)");
+        return fail(op, "workspace too small or misaligned (clibd_linear_f32_workspace_bytes)");
     return 0;
 }
 
 static int rows_check(const char* op, const float* logits, int ld, int B, int C) {
-    char msg[kErrBufLen];
-    auto fail = [&](const char* what) {
-        snprintf(msg, sizeof msg, "%s: %s", op, what);
-        return set_error(CLIBD_EINVAL, msg);
-    };
-    if (!logits) return fail("null pointer");
-    if (B <= 0 || C <= 0) return fail("non-positive shape");
-    if (C > kMaxClasses) return fail("C too large");
-    if (ld < C) return fail("ld must be >= C");
-    if (((uintptr_t)logits & 3u) != 0) return fail("logits must be 4-byte aligned");
+    if (!logits) return fail(op, "null pointer");
+    if (B <= 0 || C <= 0) return fail(op, "non-positive shape");
+    if (C > kMaxClasses) return fail(op, "C too large");
+    if (ld < C) return fail(op, "ld must be >= C");
+    if (((uintptr_t)logits & 3u) != 0) return fail(op, "logits must be 4-byte aligned");
     return 0;
 }
 
@@ -267,18 +200,10 @@ extern "C" int clibd_linear_f32_fwd(const float* x, const float* w, const float*
     const ClsWs ws = carve(workspace, B, C, D);
     hipStream_t st = (hipStream_t)stream;
     const int C16 = pad16(C);
-    hipLaunchKernelGGL(split3_kernel, dim3(grid_for((size_t)B * D)), dim3(256), 0, st, x, B, D, 1, ws.x3);
-    hipLaunchKernelGGL(split3_kernel, dim3(grid_for((size_t)C * D)), dim3(256), 0, st, w, C, D, 0, ws.w3);
     hipLaunchKernelGGL(pad_bias_kernel, dim3((C16 + 255) / 256), dim3(256), 0, st, bias, C, C16, ws.bias16);
-    if (int e = check_launch("linear_f32_fwd split")) return e;
-    if (C16 != C && hipMemsetAsync(ws.w3 + (size_t)C * 3 * D, 0, (size_t)(C16 - C) * 3 * D * 2, st) != hipSuccess)
-        return set_error(CLIBD_ELAUNCH, "linear_f32_fwd: memset failed");
-    clibd_gemm_epilogue ep = {};
-    ep.bias = ws.bias16;
-    ep.out_f32 = ws.S;
-    ep.ld_out_f32 = C16;
-    ep.split_k = 1;
-    if (int e = clibd_gemm_bf16_nt(ws.x3, 3 * D, ws.w3, 3 * D, B, C16, 3 * D, &ep, nullptr, 0, stream)) return e;
+    if (int e = split3_forward(x, w, B, C, D, ws.bias16, ws.S, ws.p, grid_for((size_t)B * D), grid_for((size_t)C * D), "linear_f32_fwd",
+                               "linear_f32_fwd split", st))
+        return e;
     hipLaunchKernelGGL(copy_cols_kernel, dim3(grid_for((size_t)B * C)), dim3(256), 0, st, ws.S, C16, B, C, out, ld_out);
     return check_launch("linear_f32_fwd copy");
 }
@@ -290,38 +215,27 @@ extern "C" int clibd_linear_f32_bwd(const float* dout, const float* x, const flo
     if ((dx && !aligned16(dx)) || (dw && !aligned16(dw))) return set_error(CLIBD_EINVAL, "linear_f32_bwd: dx and dw must be 16-byte aligned");
     const ClsWs ws = carve(workspace, B, C, D);
     hipStream_t st = (hipStream_t)stream;
-    const int Cp = pad64(C), Bp = pad64(B);   // multiples of 64: every K segment of the backward GEMMs is whole K-tiles
     if (db != nullptr) {
         if (hipMemsetAsync(db, 0, (size_t)C * 4, st) != hipSuccess) return set_error(CLIBD_ELAUNCH, "linear_f32_bwd: memset failed");
         if (int e = clibd_batch_sum_f32(dout, B, (size_t)C, db, ws.bsum, ws.bsum_bytes, stream)) return e;
     }
     if (dx == nullptr && dw == nullptr) return CLIBD_OK;
-    hipLaunchKernelGGL(split3_pad_kernel, dim3(grid_for((size_t)B * Cp)), dim3(256), 0, st, dout, C, B, C, Cp, ws.G);
-    if (int e = check_launch("linear_f32_bwd split")) return e;
-    clibd_gemm_epilogue ep = {};
-    ep.split_k = 1;
-    ep.ld_out_f32 = D;
-    if (dx != nullptr) {   // dx[i,:] = sum_c dout[i,c] w[c,:]
-        hipLaunchKernelGGL(split3_kernel, dim3(grid_for((size_t)C * D)), dim3(256), 0, st, w, C, D, 0, ws.w3);
-        if (int e = check_launch("linear_f32_bwd split w")) return e;
-        if (int e = launch_transpose3(ws.w3, C, D, D, /*hi, lo, hi*/ 0 | (1 << 2) | (2 << 4), ws.wT, Cp, st)) return e;
-        ep.out_f32 = dx;
-        if (int e = clibd_gemm_bf16_nt(ws.G, 3 * Cp, ws.wT, 3 * Cp, B, D, 3 * Cp, &ep, nullptr, 0, stream)) return e;
+    const int Cp = pad64(C);   // a multiple of 64: every K segment of the backward GEMMs is whole K-tiles
+    if (int e = split3_image(dout, C, B, C, Cp, SPLIT3_X, ws.p.G, grid_for((size_t)B * Cp), "linear_f32_bwd split", st)) return e;
+    if (dx != nullptr) {   // dx[i,:] = sum_c dout[i,c] w[c,:]: only this product reads the image of w
+        if (int e = split3_image(w, D, C, D, D, SPLIT3_Y, ws.p.y3, grid_for((size_t)C * D), "linear_f32_bwd split w", st)) return e;
+        if (int e = split3_grad_left(dx, false, B, C, D, ws.p, st)) return e;
     }
-    if (dw != nullptr) {   // dw[c,:] = sum_i dout[i,c] x[i,:]
-        hipLaunchKernelGGL(split3_kernel, dim3(grid_for((size_t)B * D)), dim3(256), 0, st, x, B, D, 1, ws.x3);
-        if (int e = check_launch("linear_f32_bwd split x")) return e;
-        if (int e = launch_transpose3(ws.G, B, Cp, C, /*hi, lo, hi*/ 0 | (2 << 2) | (0 << 4), ws.GT, Bp, st)) return e;
-        if (int e = launch_transpose3(ws.x3, B, D, D, /*hi, hi, lo*/ 0 | (1 << 2) | (2 << 4), ws.xT, Bp, st)) return e;
-        ep.out_f32 = dw;
-        if (int e = clibd_gemm_bf16_nt(ws.GT, 3 * Bp, ws.xT, 3 * Bp, C, D, 3 * Bp, &ep, nullptr, 0, stream)) return e;
+    if (dw != nullptr) {   // dw[c,:] = sum_i dout[i,c] x[i,:]: only this product reads the image of x
+        if (int e = split3_image(x, D, B, D, D, SPLIT3_X, ws.p.x3, grid_for((size_t)B * D), "linear_f32_bwd split x", st)) return e;
+        if (int e = split3_grad_right(dw, false, B, C, D, ws.p, st)) return e;
     }
     return CLIBD_OK;
 }
 
 extern "C" size_t clibd_ce_rows_workspace_bytes(int B) {
     if (B <= 0) return 0;
-    return align_up((size_t)B * sizeof(float), 256);
+    return align_up((size_t)B * sizeof(float), 256);   // the per-row loss terms
 }
 
 extern "C" int clibd_ce_rows_fwd(const float* logits, int ld, const int64_t* target, int B, int C, float* lse, float* loss,
@@ -338,7 +252,7 @@ extern "C" int clibd_ce_rows_fwd(const float* logits, int ld, const int64_t* tar
     else
         hipLaunchKernelGGL(ce_rows_fwd_kernel<false>, grid, block, 0, st, logits, ld, target, B, C, lse, rows, (unsigned*)err);
     if (int e = check_launch("ce_rows_fwd")) return e;
-    hipLaunchKernelGGL(mean_rows_kernel, dim3(1), dim3(256), 0, st, rows, B, loss);
+    hipLaunchKernelGGL(row_sum_kernel<true>, dim3(1), dim3(256), 0, st, rows, B, loss);
     return check_launch("ce_rows_fwd (loss mean)");
 }
 

@@ -134,6 +134,43 @@ __device__ __forceinline__ float wave_max(float v) {
     return rows4_max(v);
 }
 
+// ---- contracts that several units share: one summation order, one log-sum-exp update, one result order.
+// Total of v over a workgroup's 256 threads by the halving LDS tree part[t] += part[t + w], w = 128 .. 1 (`part`: 256 elements of LDS), in
+// every thread.  T: float, int, or a struct of running totals with operator+=.
+template <typename T>
+__device__ __forceinline__ T block_tree_sum(T v, T* part) {
+    part[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    return part[0];
+}
+// out[0] += sum_i v[i] (MEAN = false) or out[0] = (sum_i v[i]) / n (MEAN = true) by ONE workgroup of 256 threads: thread t adds
+// i = t, t + 256, ... in rising order, then the tree above.  The sum depends on (v, n) only: a loss or a scalar gradient repeats bit for bit.
+template <bool MEAN>
+__global__ __launch_bounds__(256) void row_sum_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
+    __shared__ float part[256];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) s += v[i];
+    s = block_tree_sum(s, part);
+    if (threadIdx.x == 0) out[0] = MEAN ? s / (float)n : out[0] + s;
+}
+
+// one term of an online log-sum-exp: (m, s) = (running max, sum of exp(term - m)); start from m = -3.0e38f, s = 0
+__device__ __forceinline__ void online_lse_add(float& m, float& s, float v) {
+    if (v > m) {
+        s = s * __expf(m - v) + 1.0f;
+        m = v;
+    } else {
+        s += __expf(v - m);
+    }
+}
+
+// (a, ia) ranks before (b, ib) in every top-k result: the larger value first, equal values by the lower index
+__device__ __forceinline__ bool ranks_before(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
+
 // erf with |abs err| <= 1.5e-7 (Abramowitz-Stegun 7.1.26); outputs are rounded to bf16 downstream
 __device__ __forceinline__ float fast_erf(float x) {
     float ax = fabsf(x);

@@ -555,21 +555,16 @@ static int tn_splitk_impl(const void* A, int lda, const void* B, int ldb, float 
                           size_t colsum_workspace_bytes, void* stream) {
     const bool b8 = b_scale > 0.f;
     const char* op = b8 ? "gemm_fp8b_tn_splitk" : "gemm_tn_splitk";
-    auto fail = [op](const char* what) {
-        char msg[kErrBufLen];
-        snprintf(msg, sizeof msg, "%s: %s", op, what);
-        return set_error(CLIBD_EINVAL, msg);
-    };
-    if (!A || !B || !out_f32 || !workspace) return fail("null pointer");
-    if (M <= 0 || Na <= 0 || Nb <= 0 || lda < Na || ldb < Nb || ld_out != Nb) return fail("bad shape (out must be dense [Na,Nb])");
-    if ((lda & 7) || (ldb & 7) || !aligned16(A) || ((uintptr_t)B & (b8 ? 7 : 15)) || !aligned16(out_f32) || !aligned16(workspace)) return fail("alignment");
+    if (!A || !B || !out_f32 || !workspace) return fail(op, "null pointer");
+    if (M <= 0 || Na <= 0 || Nb <= 0 || lda < Na || ldb < Nb || ld_out != Nb) return fail(op, "bad shape (out must be dense [Na,Nb])");
+    if ((lda & 7) || (ldb & 7) || !aligned16(A) || ((uintptr_t)B & (b8 ? 7 : 15)) || !aligned16(out_f32) || !aligned16(workspace)) return fail(op, "alignment");
     if (int e = check_workspace(op, "colsum workspace", colsum_workspace, colsum_workspace_bytes, clibd_gemm_tn_colsum_workspace_bytes(M, Na),
                                 "clibd_gemm_tn_colsum_workspace_bytes"))
         return e;
-    if (colsum_workspace && !colsum_a) return fail("a colsum workspace needs colsum_a");
+    if (colsum_workspace && !colsum_a) return fail(op, "a colsum workspace needs colsum_a");
     const int splits = gemm256_tn_splitk_launch((const unsigned short*)A, lda, B, ldb, M, Na, Nb, (float*)workspace, workspace_bytes / sizeof(float),
                                                 colsum_a, (hipStream_t)stream, (float*)colsum_workspace, b_scale);
-    if (splits <= 0) return fail("shape not supported (need M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, workspace)");
+    if (splits <= 0) return fail(op, "shape not supported (need M % 128 == 0, M >= 256, Na % 256 == 0, Nb % 256 == 0, workspace)");
     if (int e = check_launch("gemm256_tn")) return e;
     if (int e = reduce_splits_launch((const float*)workspace, splits, (size_t)Na * Nb, out_f32, accumulate, (hipStream_t)stream)) return e;
     if (!colsum_workspace) return CLIBD_OK;

@@ -15,7 +15,32 @@ inline int set_error(int code, const char* msg) {
     return code;
 }
 
+// "op: what" as the last error; returns CLIBD_EINVAL (-1): the argument checks that serve several entry points name the one that was called
+inline int fail(const char* op, const char* what) {
+    snprintf(last_error_buf(), kErrBufLen, "%s: %s", op, what);
+    return -1;
+}
+
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline int pad64(int v) { return (v + 63) / 64 * 64; }
+inline int pad16(int v) { return (v + 15) / 16 * 16; }
+
+// Carves a caller-owned workspace into pieces, each rounded up to 256 bytes.  A null base yields null pointers: the size queries run the
+// same carve function as their entry point and return total().
+struct Carver {
+    char* base;
+    size_t off = 0;
+    explicit Carver(void* b) : base((char*)b) {}
+    template <typename T>
+    T* take(size_t count) {
+        char* p = base ? base + off : nullptr;
+        off += align_up(count * sizeof(T), 256);
+        return (T*)p;
+    }
+    size_t total() const { return off; }
+};
 
 // The workspace rule of the reduction entry points (include/clibd_hip.h, "deterministic mode"): NULL with size 0 selects the atomic / plain
 // form; NULL with a size, a misaligned or a short workspace is CLIBD_EINVAL, and the message names the size query.  `need` = that query's answer.

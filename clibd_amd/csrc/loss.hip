@@ -17,7 +17,7 @@
 #include "common.h"
 #include "../../include/clibd_hip.h"
 #include "host_util.h"
-#include "split3.h"   // split3_kernel, transpose3_bf16_kernel, launch_transpose3, pad16 / pad64 (shared with classifier.hip)
+#include "split3.h"   // the split-bf16 product module: operand images, forward product, both gradient products
 
 namespace clibd {
 
@@ -40,12 +40,7 @@ __global__ __launch_bounds__(256) void softce_rows_fwd_kernel(const float* __res
     float m = -3.0e38f, s = 0.f, ts = 0.f, td = 0.f;
     for (int j = lane; j < N; j += 64) {
         const float v = sr[j] * scale;
-        if (v > m) {
-            s = s * __expf(m - v) + 1.0f;
-            m = v;
-        } else {
-            s += __expf(v - m);
-        }
+        online_lse_add(m, s, v);
         if (labels[j] == lab) {
             ts += 1.0f;
             td += v;
@@ -59,29 +54,15 @@ __global__ __launch_bounds__(256) void softce_rows_fwd_kernel(const float* __res
         const float l = mw + __logf(s);
         lse[row] = l;
         tsum_out[row] = ts;
-        row_loss[row] = l * ts - td;   // summed in a fixed order by reduce_rows_add_kernel (round 6: no float atomics on the loss path)
+        row_loss[row] = l * ts - td;   // summed in a fixed order by row_sum_kernel (round 6: no float atomics on the loss path)
     }
 }
 
-// out[0] += sum_i v[i], one workgroup, a fixed summation order (thread t takes i = t, t + 256, ...; then an LDS tree): the loss value and
-// the temperature gradient repeat bit for bit from run to run.  Rounds 1-5 accumulated both with one float atomic per row, whose order —
-// and with it the last bits of d(logit_scale), which AdamW turns into a different trajectory — changed from launch to launch.
-__global__ __launch_bounds__(256) void reduce_rows_add_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
-    __shared__ float part[256];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) s += v[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] += part[0];
-}
-
+// The loss value and the temperature gradient are fixed-order sums of per-row terms (row_sum_kernel<false>, common.h): one float atomic per
+// row (rounds 1-5) changed their last bits, and through AdamW the trajectory, from launch to launch.
 // g_ij = w * (tsum_i * exp(scale*R_ij - lse_i) - T_ij) with R = raw similarities;
 // scale * g_ij = hi + lo (bf16 each) is written as the row image [hi | hi | lo] of width 3 * Np (zero padded past N);
-// row_ds[i] = sum_j g_ij * R_ij   (dscale += their fixed-order sum, reduce_rows_add_kernel)
+// row_ds[i] = sum_j g_ij * R_ij   (dscale += their fixed-order sum, row_sum_kernel)
 __global__ __launch_bounds__(256) void softce_rows_bwd_kernel(const float* __restrict__ S, int ldS, int Nx, int N,
                                                               const int64_t* __restrict__ labels, int row0,
                                                               const float* __restrict__ lse, const float* __restrict__ tsum,
@@ -117,35 +98,21 @@ __global__ __launch_bounds__(256) void softce_rows_bwd_kernel(const float* __res
 }
 
 struct LossWs {
-    unsigned short *x3, *y3;   // [Nx,3D], [N,3D]
-    float *S, *lse, *tsum;     // [Nx,N], [Nx], [Nx]
-    float *rows;               // [Nx]: per-row loss terms (forward), then per-row d(scale) terms (backward)
-    unsigned short *G, *GT;    // [Nx,3Np] = [hi|hi|lo],  [N,3Nxp] = [hi^T|lo^T|hi^T]
-    unsigned short *xT, *yT;   // [D,3Nxp] = [hi^T|hi^T|lo^T],  [D,3Np] = [hi^T|lo^T|hi^T]
+    Split3Ws p;               // x: [Nx,D] (M = Nx), y: [N,D]; p.G is written by softce_rows_bwd_kernel
+    float *S, *lse, *tsum;    // [Nx,pad16(N)] (ld = pad16(N), columns N.. ignored), [Nx], [Nx]
+    float *rows;              // [Nx]: per-row loss terms (forward), then per-row d(scale) terms (backward)
     size_t total;
 };
 
 static LossWs carve(void* base, int Nx, int N, int D) {
     LossWs w;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = p ? p + off : nullptr;
-        off += align_up(bytes, 256);
-        return q;
-    };
-    const int Np = pad64(N), Nxp = pad64(Nx);
-    w.x3 = (unsigned short*)take((size_t)Nx * 3 * D * 2);
-    w.y3 = (unsigned short*)take((size_t)pad16(N) * 3 * D * 2);   // rows N..N16-1 zero
-    w.S = (float*)take((size_t)Nx * pad16(N) * 4);              // ld = N16, columns N.. ignored
-    w.lse = (float*)take((size_t)Nx * 4);
-    w.tsum = (float*)take((size_t)Nx * 4);
-    w.rows = (float*)take((size_t)Nx * 4);
-    w.G = (unsigned short*)take((size_t)Nx * 3 * Np * 2);
-    w.GT = (unsigned short*)take((size_t)N * 3 * Nxp * 2);
-    w.xT = (unsigned short*)take((size_t)D * 3 * Nxp * 2);
-    w.yT = (unsigned short*)take((size_t)D * 3 * Np * 2);
-    w.total = off;
+    Carver c(base);
+    w.p.carve(c, Nx, N, D);
+    w.S = c.take<float>((size_t)Nx * pad16(N));
+    w.lse = c.take<float>(Nx);
+    w.tsum = c.take<float>(Nx);
+    w.rows = c.take<float>(Nx);
+    w.total = c.total();
     return w;
 }
 
@@ -174,21 +141,12 @@ extern "C" int clibd_softce_rows_fwd(const float* x, const float* y, const int64
     const LossWs w = carve(workspace, Nx, N, D);
     if (workspace_bytes < w.total) return set_error(CLIBD_EINVAL, "softce_fwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(split3_kernel, dim3(1024), dim3(256), 0, st, x, Nx, D, 1, w.x3);
-    hipLaunchKernelGGL(split3_kernel, dim3(1024), dim3(256), 0, st, y, N, D, 0, w.y3);
-    if (int e = check_launch("softce split")) return e;
-    const int N16 = pad16(N);
-    if (N16 != N && hipMemsetAsync(w.y3 + (size_t)N * 3 * D, 0, (size_t)(N16 - N) * 3 * D * 2, st) != hipSuccess)
-        return set_error(CLIBD_ELAUNCH, "softce_fwd: memset failed");
-    clibd_gemm_epilogue ep = {};
-    ep.out_f32 = w.S;  // raw similarities <x_i, y_j>
-    ep.ld_out_f32 = N16;
-    ep.split_k = 1;
-    if (int e = clibd_gemm_bf16_nt(w.x3, 3 * D, w.y3, 3 * D, Nx, N16, 3 * D, &ep, nullptr, 0, stream)) return e;
-    hipLaunchKernelGGL(softce_rows_fwd_kernel, dim3((Nx + 3) / 4), dim3(256), 0, st, w.S, N16, Nx, N, labels, row0, scale,
+    // w.S = the raw similarities <x_i, y_j>
+    if (int e = split3_forward(x, y, Nx, N, D, nullptr, w.S, w.p, 1024, 1024, "softce_fwd", "softce split", st)) return e;
+    hipLaunchKernelGGL(softce_rows_fwd_kernel, dim3((Nx + 3) / 4), dim3(256), 0, st, w.S, pad16(N), Nx, N, labels, row0, scale,
                        w.lse, w.tsum, w.rows);
     if (int e = check_launch("softce_rows_fwd")) return e;
-    hipLaunchKernelGGL(reduce_rows_add_kernel, dim3(1), dim3(256), 0, st, w.rows, Nx, loss_sum);
+    hipLaunchKernelGGL(row_sum_kernel<false>, dim3(1), dim3(256), 0, st, w.rows, Nx, loss_sum);
     return check_launch("softce_rows_fwd (loss sum)");
 }
 
@@ -203,25 +161,15 @@ extern "C" int clibd_softce_rows_bwd(const int64_t* labels, int Nx, int N, int D
     const LossWs w = carve(workspace, Nx, N, D);
     if (workspace_bytes < w.total) return set_error(CLIBD_EINVAL, "softce_bwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const int Np = pad64(N), Nxp = pad64(Nx);   // multiples of 64: every K segment of the backward GEMMs is whole K-tiles
+    // the image of G is pad64(N) wide: every K segment of the backward GEMMs is whole K-tiles
     hipLaunchKernelGGL(softce_rows_bwd_kernel, dim3((Nx + 3) / 4), dim3(256), 0, st, w.S, pad16(N), Nx, N, labels, row0, w.lse,
-                       w.tsum, weight, weight_scale, scale, w.G, Np, w.rows);
+                       w.tsum, weight, weight_scale, scale, w.p.G, pad64(N), w.rows);
     if (int e = check_launch("softce_rows_bwd")) return e;
     if (dscale != nullptr) {
-        hipLaunchKernelGGL(reduce_rows_add_kernel, dim3(1), dim3(256), 0, st, w.rows, Nx, dscale);
+        hipLaunchKernelGGL(row_sum_kernel<false>, dim3(1), dim3(256), 0, st, w.rows, Nx, dscale);
         if (int e = check_launch("softce_rows_bwd (dscale sum)")) return e;
     }
-    // operand images, zero padded along the contraction: segment order pairs hi.hi + hi.lo + lo.hi (see the file header)
-    if (int e = launch_transpose3(w.G, Nx, Np, N, /*hi, lo, hi*/ 0 | (2 << 2) | (0 << 4), w.GT, Nxp, st)) return e;
-    if (int e = launch_transpose3(w.x3, Nx, D, D, /*hi, hi, lo*/ 0 | (1 << 2) | (2 << 4), w.xT, Nxp, st)) return e;
-    if (int e = launch_transpose3(w.y3, N, D, D, /*hi, lo, hi*/ 0 | (1 << 2) | (2 << 4), w.yT, Np, st)) return e;
-    clibd_gemm_epilogue ep = {};
-    ep.split_k = 1;
-    // dx[i,:] += sum_j G[i,j] y[j,:]      (accumulate in place through the residual path)
-    ep.out_f32 = dx; ep.ld_out_f32 = D; ep.residual_f32 = dx; ep.ld_res = D;
-    if (int e = clibd_gemm_bf16_nt(w.G, 3 * Np, w.yT, 3 * Np, Nx, D, 3 * Np, &ep, nullptr, 0, stream)) return e;
-    // dy[j,:] += sum_i G[i,j] x[i,:]
-    ep.out_f32 = dy; ep.residual_f32 = dy;
-    if (int e = clibd_gemm_bf16_nt(w.GT, 3 * Nxp, w.xT, 3 * Nxp, N, D, 3 * Nxp, &ep, nullptr, 0, stream)) return e;
-    return CLIBD_OK;
+    // dx[i,:] += sum_j G[i,j] y[j,:] and dy[j,:] += sum_i G[i,j] x[i,:], accumulated in place
+    if (int e = split3_grad_left(dx, true, Nx, N, D, w.p, st)) return e;
+    return split3_grad_right(dy, true, Nx, N, D, w.p, st);
 }

@@ -119,13 +119,17 @@ __global__ __launch_bounds__(256) void ntxent_fwd_kernel(const unsigned short* _
 }
 
 // Row statistics from the column slices' partials, in slice order; lse[i] for the backward; loss = sum_i (lse_i - pos_i) / N and
-// top1 = #{i : pos_i >= best negative}: one workgroup, a fixed order (thread t takes i = t, t + 256, ...; then an LDS tree)
+// top1 = #{i : pos_i >= best negative}: one workgroup, a fixed order (thread t takes i = t, t + 256, ...; then block_tree_sum)
+struct NtxTotals {
+    float loss;
+    int top1;
+    __device__ NtxTotals& operator+=(const NtxTotals& o) { loss += o.loss; top1 += o.top1; return *this; }
+};
+
 __global__ __launch_bounds__(256) void ntxent_reduce_kernel(const float4* __restrict__ stat, int nslice, int N, int Np,
                                                             float* __restrict__ lse, float* __restrict__ loss, int* __restrict__ top1) {
-    __shared__ float part[256];
-    __shared__ int parti[256];
-    float s = 0.f;
-    int k = 0;
+    __shared__ NtxTotals part[256];
+    NtxTotals t = {0.f, 0};
     for (int i = threadIdx.x; i < N; i += 256) {
         float M = NTX_NEG, P = NTX_NEG, Mn = NTX_NEG, S = 0.f;
         for (int q = 0; q < nslice; ++q) M = fmaxf(M, stat[(size_t)q * Np + i].x);
@@ -137,22 +141,13 @@ __global__ __launch_bounds__(256) void ntxent_reduce_kernel(const float4* __rest
         }
         const float l = M + __logf(S);
         lse[i] = l;
-        s += l - P;
-        k += P >= Mn ? 1 : 0;
+        t.loss += l - P;
+        t.top1 += P >= Mn ? 1 : 0;
     }
-    part[threadIdx.x] = s;
-    parti[threadIdx.x] = k;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            part[threadIdx.x] += part[threadIdx.x + w];
-            parti[threadIdx.x] += parti[threadIdx.x + w];
-        }
-        __syncthreads();
-    }
+    t = block_tree_sum(t, part);
     if (threadIdx.x == 0) {
-        loss[0] = part[0] / (float)N;
-        if (top1 != nullptr) top1[0] = parti[0];
+        loss[0] = t.loss / (float)N;
+        if (top1 != nullptr) top1[0] = t.top1;
     }
 }
 
@@ -290,8 +285,6 @@ __global__ __launch_bounds__(256) void ntxent_bwd_rows_kernel(const float* __res
     for (int c = lane; c < D; c += 64) df[(size_t)row * D + c] = sc * (gr[c] - (fr[c] * inv) * dot);
 }
 
-static inline size_t ntx_align(size_t v) { return (v + 255) / 256 * 256; }
-
 struct NtxWs {
     unsigned short *fhi, *flo;     // [Np, Dp]
     unsigned short *fthi, *ftlo;   // [Dp, Np], j permuted within groups of 32 (backward)
@@ -306,29 +299,22 @@ static NtxWs ntx_carve(void* base, int N, int D) {
     NtxWs w;
     w.Np = (N + 127) / 128 * 128;
     w.Dp = (D + 31) / 32 * 32;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = p ? p + off : nullptr;
-        off += ntx_align(bytes);
-        return q;
-    };
+    Carver c(base);
     const size_t nd = (size_t)w.Np * w.Dp;
-    w.fhi = (unsigned short*)take(nd * 2);
-    w.flo = (unsigned short*)take(nd * 2);
-    w.fthi = (unsigned short*)take(nd * 2);
-    w.ftlo = (unsigned short*)take(nd * 2);
-    w.g = (float*)take(nd * 4);
-    w.inv_norm = (float*)take((size_t)w.Np * 4);
-    w.lse = (float*)take((size_t)w.Np * 4);
+    w.fhi = c.take<unsigned short>(nd);
+    w.flo = c.take<unsigned short>(nd);
+    w.fthi = c.take<unsigned short>(nd);
+    w.ftlo = c.take<unsigned short>(nd);
+    w.g = c.take<float>(nd);
+    w.inv_norm = c.take<float>(w.Np);
+    w.lse = c.take<float>(w.Np);
     w.nslice = w.Np / 128 < NTX_FWD_SLICES ? w.Np / 128 : NTX_FWD_SLICES;   // a function of N alone: the summation order is fixed
-    w.part = (float4*)take((size_t)w.nslice * w.Np * 16);
-    w.total = off;
+    w.part = c.take<float4>((size_t)w.nslice * w.Np);
+    w.total = c.total();
     return w;
 }
 
 static int ntx_check(const char* op, const float* f, int N, int D, const void* ws, size_t ws_bytes) {
-    char msg[kErrBufLen];
     const char* why = nullptr;
     if (!f) why = "null feature pointer";
     else if (N < 4) why = "N must be at least 4 (two views of two samples)";
@@ -338,9 +324,7 @@ static int ntx_check(const char* op, const float* f, int N, int D, const void* w
     else if (!ws) why = "null workspace pointer";
     else if (!aligned16(ws)) why = "workspace must be 16-byte aligned";
     else if (ws_bytes < ntx_carve(nullptr, N, D).total) why = "workspace too small (clibd_ntxent_workspace_bytes)";
-    if (!why) return 0;
-    snprintf(msg, sizeof msg, "%s: %s", op, why);
-    return set_error(CLIBD_EINVAL, msg);
+    return why ? fail(op, why) : 0;
 }
 
 }  // namespace clibd

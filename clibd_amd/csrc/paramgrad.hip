@@ -324,7 +324,6 @@ using namespace clibd;
 
 // ---- the reductions: one entry point each.  NULL workspace: float atomics; with a workspace (deterministic mode, see the header of this
 // file) the same kernel stores one partial per block / chunk and ordered_colsum_kernel adds them in a fixed order.
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr int PG_ORDERED_BLOCKS = 1024;   // cap of the partial count of the row-chunk kernels (grid-stride beyond it)
 constexpr int TT_ORDERED_BLOCKS = 512;
 // blocks of a row-chunk kernel: one per PG_ROWS rows in the atomic form, capped where every block owns a workspace row
@@ -385,14 +384,13 @@ static EmbedWs embed_ws_layout(char* base, int M, int H, int type_vocab) {
     const int ntiles = (M + EMB_TILE - 1) / EMB_TILE, nchunks = (M + EMB_CHUNK - 1) / EMB_CHUNK;
     const int ttb = row_chunk_blocks(M, true, TT_ORDERED_BLOCKS);
     EmbedWs w{};
-    size_t o = 0;
-    auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += al256(b); return p; };
-    w.ka = (int*)take((size_t)M * 4); w.va = (int*)take((size_t)M * 4);
-    w.kb = (int*)take((size_t)M * 4); w.vb = (int*)take((size_t)M * 4);
-    w.hist = (int*)take((size_t)256 * ntiles * 4);
-    w.head = (float*)take((size_t)nchunks * H * 4); w.own = (float*)take((size_t)nchunks * H * 4);
-    w.tt = (float*)take((size_t)ttb * type_vocab * H * 4);
-    w.bytes = o;
+    Carver c(base);
+    w.ka = c.take<int>(M); w.va = c.take<int>(M);
+    w.kb = c.take<int>(M); w.vb = c.take<int>(M);
+    w.hist = c.take<int>((size_t)256 * ntiles);
+    w.head = c.take<float>((size_t)nchunks * H); w.own = c.take<float>((size_t)nchunks * H);
+    w.tt = c.take<float>((size_t)ttb * type_vocab * H);
+    w.bytes = c.total();
     return w;
 }
 

@@ -1,57 +1,35 @@
-// The split-bf16 operand images shared by the fp32-grade products (loss.hip: K9's similarity; classifier.hip: the linear-probe head).
+// The split-bf16 product module (split3.hip): the fp32-grade products of loss.hip (K9's similarity) and classifier.hip (the linear-probe head).
 //   v = hi + lo (bf16 each);  <x, y> ~ hi·hi + hi·lo + lo·hi  as ONE NT GEMM with K = 3D over [hi|hi|lo] (x side) and [hi|lo|hi] (y side).
-// The kernels have internal linkage: each translation unit that includes this header carries its own copy of the host stubs.
+// Kernels, segment orders, padding and GEMM calls live in split3.hip, once in the code object; declarations only here (not C-ABI symbols).
 #pragma once
-#include "common.h"
 #include "host_util.h"
 
 namespace clibd {
 
-// img3[r, 0:D] = hi, img3[r, D:2D] = MID, img3[r, 2D:3D] = LAST  with (MID,LAST) = (hi,lo) for x, (lo,hi) for y
-static __global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ in, int R, int D, int x_side,
-                                                            unsigned short* __restrict__ out) {
-    const size_t total = (size_t)R * D;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = i / D;
-        const int c = (int)(i - r * D);
-        const float v = in[i];
-        const unsigned short hi = f2bf(v);
-        const unsigned short lo = f2bf(v - bf2f(hi));
-        unsigned short* o = out + r * 3 * (size_t)D;
-        o[c] = hi;
-        o[D + c] = x_side ? hi : lo;
-        o[2 * D + c] = x_side ? lo : hi;
-    }
-}
+enum Split3Side { SPLIT3_Y = 0, SPLIT3_X = 1 };   // [hi|lo|hi] / [hi|hi|lo]
 
-// out[c, k * Rp + r] = in[r, seg(k) * W + c] for the three column segments of a [R, 3W] image (seg(k) = 2 bits of `map` each),
-// c < C <= W, r < Rp with zeros for r >= R: the K-concatenated operand images of the backward GEMMs, transposed in one launch.
-static __global__ __launch_bounds__(256) void transpose3_bf16_kernel(const unsigned short* __restrict__ in, int R, int W, int C, int map,
-                                                                     unsigned short* __restrict__ out, int Rp) {
-    __shared__ unsigned short tile[64][66];
-    const int k = blockIdx.z;
-    const int seg = (map >> (2 * k)) & 3;
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    for (int i = ty; i < 64; i += 4) {
-        const int r = r0 + i, c = c0 + tx;
-        tile[i][tx] = (r < R && c < C) ? in[(size_t)r * 3 * W + (size_t)seg * W + c] : (unsigned short)0;
-    }
-    __syncthreads();
-    for (int i = ty; i < 64; i += 4) {
-        const int c = c0 + i, r = r0 + tx;
-        if (c < C && r < Rp) out[(size_t)c * 3 * Rp + (size_t)k * Rp + r] = tile[tx][i];
-    }
-}
+// The operand images of the products of x [M,D] and y [N,D], carved in this order.
+struct Split3Ws {
+    unsigned short *x3, *y3;   // [M,3D] = [hi|hi|lo],  [pad16(N),3D] = [hi|lo|hi] (rows N.. zero)
+    unsigned short *G, *GT;    // the coefficients g [M,N]: [M,3Np] = [hi|hi|lo],  [N,3Mp] = [hi^T|lo^T|hi^T]      (Np = pad64(N), Mp = pad64(M))
+    unsigned short *xT, *yT;   // [D,3Mp] = [hi^T|hi^T|lo^T],  [D,3Np] = [hi^T|lo^T|hi^T]
+    void carve(Carver& c, int M, int N, int D);
+};
 
-static inline int launch_transpose3(const unsigned short* in, int R, int W, int C, int map, unsigned short* out, int Rp, hipStream_t st) {
-    dim3 grid((C + 63) / 64, (Rp + 63) / 64, 3);
-    hipLaunchKernelGGL(transpose3_bf16_kernel, grid, dim3(256), 0, st, in, R, W, C, map, out, Rp);
-    return check_launch("split-bf16 transpose3");
-}
+// out[r, 0:Cp | Cp:2Cp | 2Cp:3Cp] = the side's image of in[r, 0:C] (row stride ld_in), segments zero padded to Cp columns; `grid` workgroups
+// of a grid-stride loop; `what` names the launch in an error.
+int split3_image(const float* in, int ld_in, int R, int C, int Cp, Split3Side side, unsigned short* out, unsigned grid, const char* what,
+                 hipStream_t st);
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-static inline int pad64(int v) { return (v + 63) / 64 * 64; }
-static inline int pad16(int v) { return (v + 15) / 16 * 16; }
+// out[M, pad16(N)] (ld = pad16(N), columns N.. are those of zero rows) = x · yᵀ (+ bias16[pad16(N)] if given).  Splits x into ws.x3 and y
+// into ws.y3 with grid_x / grid_y workgroups and zeroes the padded rows of ws.y3.  `op` names the entry point in the memset's error,
+// `what` the split launches.
+int split3_forward(const float* x, const float* y, int M, int N, int D, const float* bias16, float* out, const Split3Ws& ws, unsigned grid_x,
+                   unsigned grid_y, const char* op, const char* what, hipStream_t st);
+
+// dx[M,D] (+)= g · y from ws.G (the caller writes the [hi|hi|lo] image of g, e.g. with split3_image) and ws.y3; uses ws.yT
+int split3_grad_left(float* dx, bool accumulate, int M, int N, int D, const Split3Ws& ws, hipStream_t st);
+// dy[N,D] (+)= gᵀ · x from ws.G and ws.x3; uses ws.GT and ws.xT
+int split3_grad_right(float* dy, bool accumulate, int M, int N, int D, const Split3Ws& ws, hipStream_t st);
 
 }  // namespace clibd

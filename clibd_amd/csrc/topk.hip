@@ -26,13 +26,10 @@ constexpr int TK_KMAX = 8;
 constexpr float TK_NEG = -3.0e38f;
 constexpr int TK_NOIDX = 0x7fffffff;
 
-// (v, id) goes before (bv, bi) in the result order: larger score first, equal scores by ascending key index
-__device__ __forceinline__ bool tk_before(float v, int id, float bv, int bi) { return (v > bv) || (v == bv && id < bi); }
-
 __device__ __forceinline__ void tk_insert(float v, int id, float (&bv)[TK_KMAX], int (&bi)[TK_KMAX]) {
 #pragma unroll
     for (int j = 0; j < TK_KMAX; ++j) {
-        const bool better = tk_before(v, id, bv[j], bi[j]);
+        const bool better = ranks_before(v, id, bv[j], bi[j]);
         const float tv = better ? bv[j] : v;
         const int ti = better ? bi[j] : id;
         bv[j] = better ? v : bv[j];
@@ -130,13 +127,13 @@ __global__ __launch_bounds__(256) void topk_ip_stream_kernel(const float* __rest
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int key = kbase + (r & 3) + 8 * (r >> 2);
-            any_in = any_in || (key < Nk && tk_before(acc[r], key, bv[TK_KMAX - 1], bi[TK_KMAX - 1]));
+            any_in = any_in || (key < Nk && ranks_before(acc[r], key, bv[TK_KMAX - 1], bi[TK_KMAX - 1]));
         }
         if (__any(any_in)) {   // wave vote: after the first tiles a score rarely beats the tail of a list
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = kbase + (r & 3) + 8 * (r >> 2);
-                if (key < Nk && tk_before(acc[r], key, bv[TK_KMAX - 1], bi[TK_KMAX - 1])) tk_insert(acc[r], key, bv, bi);
+                if (key < Nk && ranks_before(acc[r], key, bv[TK_KMAX - 1], bi[TK_KMAX - 1])) tk_insert(acc[r], key, bv, bi);
             }
         }
     }
@@ -165,7 +162,7 @@ __global__ __launch_bounds__(256) void topk_ip_stream_kernel(const float* __rest
                 for (int c = 0; c < 4 * TK_KMAX; ++c) {
                     const float v = cand_v[ql][c];
                     const int id = cand_i[ql][c];
-                    if (id != TK_NOIDX && tk_before(pv, pi, v, id) && tk_before(v, id, cv, ci)) { cv = v; ci = id; }
+                    if (id != TK_NOIDX && ranks_before(pv, pi, v, id) && ranks_before(v, id, cv, ci)) { cv = v; ci = id; }
                 }
                 pv = cv;
                 pi = ci;
@@ -199,7 +196,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
             for (int j = 0; j < TK_KMAX; ++j) {
                 const float v = v8[j];
                 const int id = i8[j];
-                if (id != TK_NOIDX && tk_before(pv, pi, v, id) && tk_before(v, id, cv, ci)) { cv = v; ci = id; }
+                if (id != TK_NOIDX && ranks_before(pv, pi, v, id) && ranks_before(v, id, cv, ci)) { cv = v; ci = id; }
             }
         }
         pv = cv;
@@ -220,6 +217,16 @@ static int topk_splits(int Q, int Nk) {
     return nsplit;
 }
 
+// The per-split lists [nsplit][Q][8] of clibd_topk_ip: one dense block whose size is not rounded (the size query has always reported it so).
+struct TopkWs { int nsplit; float* part_v; int* part_i; size_t total; };
+
+static TopkWs topk_carve(void* base, int Q, int Nk) {
+    const int nsplit = topk_splits(Q, Nk);
+    const size_t lists = (size_t)nsplit * (size_t)Q * TK_KMAX;
+    float* v = (float*)base;
+    return {nsplit, v, base ? (int*)(v + lists) : nullptr, nsplit > 1 ? lists * (sizeof(float) + sizeof(int)) : 16};
+}
+
 
 // ================================================================================================================================
 // Pre-filtered search (round 4): the same top-k, indices and similarities bit-identical to clibd_topk_ip, at the bf16 MFMA rate.
@@ -237,7 +244,7 @@ static int topk_splits(int Q, int Nk) {
 //      key above the line may have been pushed out of it: the query is flagged in `overflow` and the caller re-runs it through
 //      clibd_topk_ip (exactness never depends on the data; only the speed does).
 // Random unit vectors at 1 k x 410 k x 768: ~12 keys above the line per query, ~3 per list.
-// wave-wide best (score, index) pair under tk_before, in every lane: the maximum score, then the lowest index among the lanes that
+// wave-wide best (score, index) pair under ranks_before, in every lane: the maximum score, then the lowest index among the lanes that
 // hold it.  DPP / v_permlane reductions only (common.h: no LDS-crossbar instruction); key indices are < 2^24, exact as floats.
 __device__ __forceinline__ void tk_wave_best(float& v, int& id) {
     const float m = wave_max(v);
@@ -364,13 +371,13 @@ __global__ __launch_bounds__(256) void topk_bf16_stream_kernel(const unsigned sh
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = kbase + (r & 3) + 8 * (r >> 2);
-                any_in = any_in || (key < Nk && tk_before(acc[h][r], key, bv[TK_KMAX - 1], bi[TK_KMAX - 1]));
+                any_in = any_in || (key < Nk && ranks_before(acc[h][r], key, bv[TK_KMAX - 1], bi[TK_KMAX - 1]));
             }
             if (__any(any_in)) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kbase + (r & 3) + 8 * (r >> 2);
-                    if (key < Nk && tk_before(acc[h][r], key, bv[TK_KMAX - 1], bi[TK_KMAX - 1])) tk_insert(acc[h][r], key, bv, bi);
+                    if (key < Nk && ranks_before(acc[h][r], key, bv[TK_KMAX - 1], bi[TK_KMAX - 1])) tk_insert(acc[h][r], key, bv, bi);
                 }
             }
         }
@@ -410,7 +417,7 @@ __global__ __launch_bounds__(256) void topk_rescore_kernel(const float* __restri
         for (int e = lane; e < nent; e += 64) {
             const float v = ent_v(e);
             const int id = ent_i(e);
-            if (id != TK_NOIDX && tk_before(pv, pi, v, id) && tk_before(v, id, bvv, bii)) { bvv = v; bii = id; }
+            if (id != TK_NOIDX && ranks_before(pv, pi, v, id) && ranks_before(v, id, bvv, bii)) { bvv = v; bii = id; }
         }
         tk_wave_best(bvv, bii);
         pv = bvv;
@@ -457,7 +464,7 @@ __global__ __launch_bounds__(256) void topk_rescore_kernel(const float* __restri
     for (int r = 0; r < k; ++r) {
         float bvv = TK_NEG;
         int bii = TK_NOIDX;
-        if (eid != TK_NOIDX && tk_before(pv, pi, ev, eid)) { bvv = ev; bii = eid; }
+        if (eid != TK_NOIDX && ranks_before(pv, pi, ev, eid)) { bvv = ev; bii = eid; }
         tk_wave_best(bvv, bii);
         pv = bvv;
         pi = bii;
@@ -477,14 +484,30 @@ static int topk_fast_splits(int Q, int Nk) {
     return nsplit;
 }
 
+// bf16 queries [Q, D], ||q|| [Q], the lists [nsplit][Q][2][8]
+struct TopkFastWs { int nsplit; unsigned short* q16; float* qn; float* part_v; int* part_i; size_t total; };
+
+static TopkFastWs topk_fast_carve(void* base, int Q, int Nk, int D) {
+    TopkFastWs w;
+    w.nsplit = topk_fast_splits(Q, Nk);
+    Carver c(base);
+    w.q16 = c.take<unsigned short>((size_t)Q * D);
+    w.qn = c.take<float>(Q);
+    // the tail, written out: `lists` floats, then `lists` ints, unrounded, then the 256 bytes the size query has always added (observable)
+    const size_t lists = (size_t)w.nsplit * Q * 2 * TK_KMAX;
+    w.part_v = base ? (float*)((char*)base + c.total()) : nullptr;
+    w.part_i = base ? (int*)(w.part_v + lists) : nullptr;
+    w.total = c.total() + lists * (sizeof(float) + sizeof(int)) + 256;
+    return w;
+}
+
 }  // namespace clibd
 
 using namespace clibd;
 
 extern "C" size_t clibd_topk_ip_workspace_bytes(int Q, int Nk) {
     if (Q <= 0 || Nk <= 0) return 0;
-    const int nsplit = topk_splits(Q, Nk);
-    return nsplit > 1 ? (size_t)nsplit * (size_t)Q * TK_KMAX * (sizeof(float) + sizeof(int)) : 16;
+    return topk_carve(nullptr, Q, Nk).total;
 }
 
 extern "C" int clibd_topk_ip(const float* q, const float* keys, int Q, int Nk, int D, int k, int64_t* out_idx, float* out_sim,
@@ -494,19 +517,18 @@ extern "C" int clibd_topk_ip(const float* q, const float* keys, int Q, int Nk, i
     if (k < 1 || k > TK_KMAX || k > Nk) return set_error(CLIBD_EINVAL, "topk_ip: need 1 <= k <= min(8, Nk)");
     if (D % 4 != 0) return set_error(CLIBD_EINVAL, "topk_ip: D must be a multiple of 4");
     if (!aligned16(q) || !aligned16(keys) || !aligned16(workspace)) return set_error(CLIBD_EINVAL, "topk_ip: alignment");
-    if (workspace_bytes < clibd_topk_ip_workspace_bytes(Q, Nk)) return set_error(CLIBD_EINVAL, "topk_ip: workspace too small");
-    const int nsplit = topk_splits(Q, Nk);
+    const TopkWs w = topk_carve(workspace, Q, Nk);
+    if (workspace_bytes < w.total) return set_error(CLIBD_EINVAL, "topk_ip: workspace too small");
+    const int nsplit = w.nsplit;
     const int ntiles = (Nk + 63) / 64;
     const int tiles_per_split = (ntiles + nsplit - 1) / nsplit;
     hipStream_t st = (hipStream_t)stream;
-    float* part_v = (float*)workspace;
-    int* part_i = (int*)(part_v + (size_t)nsplit * Q * TK_KMAX);
     dim3 grid((unsigned)((Q + 63) / 64), (unsigned)nsplit);
     hipLaunchKernelGGL(topk_ip_stream_kernel, grid, dim3(256), 0, st, q, keys, Q, Nk, D, tiles_per_split, nsplit, k, (long long*)out_idx,
-                       out_sim, part_v, part_i);
+                       out_sim, w.part_v, w.part_i);
     if (int e = check_launch("topk_ip_stream")) return e;
     if (nsplit > 1) {
-        hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, (const float*)part_v, (const int*)part_i, Q,
+        hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, (const float*)w.part_v, (const int*)w.part_i, Q,
                            nsplit, k, (long long*)out_idx, out_sim);
         return check_launch("topk_merge");
     }
@@ -527,13 +549,7 @@ extern "C" int clibd_topk_prepare_keys(const float* keys, int Nk, int D, void* k
 
 extern "C" size_t clibd_topk_ip_fast_workspace_bytes(int Q, int Nk, int D) {
     if (Q <= 0 || Nk <= 0 || D <= 0) return 0;
-    const int nsplit = topk_fast_splits(Q, Nk);
-    size_t b = (size_t)Q * D * 2;                       // bf16 queries
-    b = (b + 255) / 256 * 256;
-    b += (size_t)Q * sizeof(float);                    // ||q||
-    b = (b + 255) / 256 * 256;
-    b += (size_t)nsplit * Q * 2 * TK_KMAX * (sizeof(float) + sizeof(int));
-    return b + 256;
+    return topk_fast_carve(nullptr, Q, Nk, D).total;
 }
 
 extern "C" int clibd_topk_ip_fast(const float* q, const float* keys, const void* keys_bf16, const float* max_norm, int Q, int Nk, int D, int k,
@@ -545,26 +561,20 @@ extern "C" int clibd_topk_ip_fast(const float* q, const float* keys, const void*
     // below 2^24), and the band TK_C leaves 5.9e-4 of headroom for the two fp32 accumulations, whose worst case grows as 2 D 2^-23.
     if (Nk >= TK_FAST_MAX_KEYS || D > TK_FAST_MAX_D) return set_error(CLIBD_EINVAL, "topk_ip_fast: needs Nk < 2^24 and D <= 2048 (use clibd_topk_ip)");
     if (!aligned16(q) || !aligned16(keys) || !aligned16(keys_bf16) || !aligned16(workspace)) return set_error(CLIBD_EINVAL, "topk_ip_fast: alignment");
-    if (workspace_bytes < clibd_topk_ip_fast_workspace_bytes(Q, Nk, D)) return set_error(CLIBD_EINVAL, "topk_ip_fast: workspace too small");
-    const int nsplit = topk_fast_splits(Q, Nk);
+    const TopkFastWs w = topk_fast_carve(workspace, Q, Nk, D);
+    if (workspace_bytes < w.total) return set_error(CLIBD_EINVAL, "topk_ip_fast: workspace too small");
+    const int nsplit = w.nsplit;
     const int ntiles = (Nk + TB_K - 1) / TB_K;
     const int tiles_per_split = (ntiles + nsplit - 1) / nsplit;
-    char* w = (char*)workspace;
-    unsigned short* q16 = (unsigned short*)w;
-    size_t off = ((size_t)Q * D * 2 + 255) / 256 * 256;
-    float* qn = (float*)(w + off);
-    off = (off + (size_t)Q * sizeof(float) + 255) / 256 * 256;
-    float* part_v = (float*)(w + off);
-    int* part_i = (int*)(part_v + (size_t)nsplit * Q * 2 * TK_KMAX);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(topk_prepare_queries_kernel, dim3((unsigned)min((Q + 3) / 4, 4096)), dim3(256), 0, st, q, Q, D, q16, qn);
+    hipLaunchKernelGGL(topk_prepare_queries_kernel, dim3((unsigned)min((Q + 3) / 4, 4096)), dim3(256), 0, st, q, Q, D, w.q16, w.qn);
     if (int e = check_launch("topk_prepare_queries")) return e;
     constexpr int LDS = 2 * (TB_Q + TB_K) * TB_LD;
     hipFuncSetAttribute((const void*)topk_bf16_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipLaunchKernelGGL(topk_bf16_stream_kernel, dim3((unsigned)((Q + TB_Q - 1) / TB_Q), (unsigned)nsplit), dim3(256), LDS, st, (const unsigned short*)q16,
-                       (const unsigned short*)keys_bf16, Q, Nk, D, tiles_per_split, part_v, part_i);
+    hipLaunchKernelGGL(topk_bf16_stream_kernel, dim3((unsigned)((Q + TB_Q - 1) / TB_Q), (unsigned)nsplit), dim3(256), LDS, st, (const unsigned short*)w.q16,
+                       (const unsigned short*)keys_bf16, Q, Nk, D, tiles_per_split, w.part_v, w.part_i);
     if (int e = check_launch("topk_bf16_stream")) return e;
-    hipLaunchKernelGGL(topk_rescore_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, q, keys, (const float*)qn, max_norm, (const float*)part_v,
-                       (const int*)part_i, Q, D, nsplit, k, (long long*)out_idx, out_sim, (int*)overflow);
+    hipLaunchKernelGGL(topk_rescore_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, q, keys, (const float*)w.qn, max_norm, (const float*)w.part_v,
+                       (const int*)w.part_i, Q, D, nsplit, k, (long long*)out_idx, out_sim, (int*)overflow);
     return check_launch("topk_rescore");
 }

@@ -3,7 +3,7 @@
 Rounds 1-5 accumulated the loss value, d(logit_scale), the trainable heads' bias gradients and — at batches below 8192 token rows — the
 adapters' gradients with float atomics: two runs of the same step agreed to ~1e-7 only, AdamW turned that into different trajectories, and
 every "gradient fidelity after 40 training steps" figure of the fp8 modes (tests/test_fp8_gpu.py) scattered by +-0.005 from run to run.
-Every sum on the frozen-base path now has a fixed order (csrc/loss.hip reduce_rows_add_kernel, csrc/gemm.hip colsum_partials_kernel,
+Every sum on the frozen-base path now has a fixed order (csrc/common.h row_sum_kernel, csrc/gemm.hip colsum_partials_kernel,
 csrc/lora.hip lora_reduce_kernel at every whole-slab M), so: same parameters + same batch + same dropout seed -> the same bits.
 
 (Full fine-tune mode keeps float atomics in the LayerNorm / embedding parameter gradients: csrc/layernorm.hip PG, csrc/paramgrad.hip.)
