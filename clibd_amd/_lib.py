@@ -174,6 +174,14 @@ ROLLOUT_SIGNATURES = {
     "clibd_rollout_chain": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
+# the INSECT / BZSL workflow (include/clibd_hip_insect.h): a seventh additive table, bound after the other six
+INSECT_SIGNATURES = {
+    "clibd_class_mean_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "clibd_class_mean_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
+    "clibd_logits_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -198,7 +206,7 @@ def load() -> C.CDLL:
         )
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items())
-                              + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items())):
+                              + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(INSECT_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1464,3 +1464,61 @@ def rollout_chain(maps: torch.Tensor, S: int) -> torch.Tensor:
     out = torch.empty((B, S - 1), dtype=F32, device=maps.device)
     check(_lib.load().clibd_rollout_chain(maps.data_ptr(), L, B, S, ld, out.data_ptr(), _stream()), "rollout_chain")
     return out
+
+
+# ---- the INSECT / BZSL workflow (include/clibd_hip_insect.h) ---------------------------------------------------------------------------
+def class_mean(x: torch.Tensor, labels: torch.Tensor, num_classes: int, transposed: bool = False, out: Optional[torch.Tensor] = None,
+               error: Optional[torch.Tensor] = None):
+    """The class means in numpy's order (clibd_class_mean_f32): x fp32 [N, D] with unit inner stride (a row stride above D is taken as it
+    is), labels int32 [N].  Returns (mean, count int32 [C], error int32 [1]): mean fp32 [C, D], or [D, C] with transposed=True (`out`: a
+    2-D fp32 tensor of that shape with unit inner stride to write into).  mean[c] = ((x[i1] + x[i2]) + ...) / n over the rows of class c
+    in ascending order, bit for bit np.sum(rows, axis=0) / len(rows); an empty class is a zero row.  A label outside [0, C) is skipped
+    and sets bit 0 of `error` (a fresh zero word unless one is passed); nothing is read back here."""
+    _chk(x, F32, "x", contiguous=False)
+    _chk(labels, I32, "labels")
+    ld_x = _rowmajor(x, "x")
+    N, D = x.shape
+    Ccls = int(num_classes)
+    if tuple(labels.shape) != (N,):
+        raise ValueError(f"class_mean: labels must be [{N}]")
+    if N < 1 or D < 1 or not 1 <= Ccls <= 65536 or N * D >= 2 ** 31:
+        raise ValueError("class_mean: need N >= 1, D >= 1, 1 <= C <= 65536 and N * D < 2^31")
+    if N > 1 and ld_x < D:
+        raise ValueError("class_mean: the rows of x overlap")
+    dev = x.device
+    shape = (D, Ccls) if transposed else (Ccls, D)
+    if out is None:
+        out = torch.empty(shape, dtype=F32, device=dev)
+    else:
+        _chk(out, F32, "out", contiguous=False)
+        if tuple(out.shape) != shape:
+            raise ValueError(f"class_mean: out must be {list(shape)}")
+    ld_mean = _rowmajor(out, "out")
+    count = torch.empty((Ccls,), dtype=I32, device=dev)
+    if error is None:
+        error = torch.zeros((1,), dtype=I32, device=dev)
+    else:
+        _chk(error, I32, "error")
+    lib = _lib.load()
+    ws = _workspace("class_mean", int(lib.clibd_class_mean_workspace_bytes(N, Ccls)), dev)
+    check(lib.clibd_class_mean_f32(x.data_ptr(), max(ld_x, D), labels.data_ptr(), N, Ccls, D, out.data_ptr(), max(ld_mean, shape[1]), int(bool(transposed)),
+                                   count.data_ptr(), error.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "class_mean_f32")
+    return out, count, error
+
+
+def logits_topk(logits: torch.Tensor, k: int = 5):
+    """torch.sort(logits, dim=1, descending=True, stable=True) cut to k columns (clibd_logits_topk): (val fp32 [B, k] — the logits
+    themselves —, idx int64 [B, k]); equal values resolve to the lower index, -inf is a value like any other, NaN is not supported.
+    1 <= k <= 8, and k > C raises as in softmax_topk."""
+    _chk(logits, F32, "logits", contiguous=False)
+    ld = _rowmajor(logits, "logits")
+    B, Ccls = logits.shape
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("logits_topk: k must be in 1..8")
+    if k > Ccls:
+        raise RuntimeError("logits_topk: selected index k out of range")
+    val = torch.empty((B, k), dtype=F32, device=logits.device)
+    idx = torch.empty((B, k), dtype=I64, device=logits.device)
+    check(_lib.load().clibd_logits_topk(logits.data_ptr(), max(ld, Ccls), B, Ccls, k, val.data_ptr(), idx.data_ptr(), _stream()), "logits_topk")
+    return val, idx
