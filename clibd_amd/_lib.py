@@ -182,6 +182,13 @@ INSECT_SIGNATURES = {
     "clibd_logits_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
+# the pre-extracted-feature MLP towers (include/clibd_hip_mlp.h): an eighth additive table, bound after the other seven
+MLP_SIGNATURES = {
+    "clibd_mlp_linear_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "clibd_mlp_linear_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "clibd_mlp_linear_wgrad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -206,7 +213,7 @@ def load() -> C.CDLL:
         )
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items())
-                              + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(INSECT_SIGNATURES.items())):
+                              + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(INSECT_SIGNATURES.items()) + list(MLP_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -171,6 +171,10 @@ def _contrastive(features, labels, logit_scale, rank, world, bind_to=None, no_im
     for f in feats:
         if f.shape != shape or f.dim() != 2:
             raise ValueError("all modality features must be [batch, dim] with equal shapes")
+    if shape[1] % 64:
+        # the loss kernels contract whole 64-wide tiles (clibd_softce_rows_*: D % 64 == 0).  Zero columns change neither a norm nor a dot
+        # product, and autograd drops their gradient: an embedding width such as a feature tower's output_dim = 48 runs padded.
+        feats = [torch.nn.functional.pad(f, (0, 64 - shape[1] % 64)) for f in feats]
     if not torch.is_tensor(logit_scale):
         logit_scale = torch.tensor(float(logit_scale), dtype=F32, device=dev)
     if use_dist is None:

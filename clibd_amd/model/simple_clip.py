@@ -5,7 +5,8 @@ forward(image_input, dna_input, language_input) ->
     (image_output, dna_output, language_output, logit_scale.exp(), logit_bias)
 with every present tower output L2-normalised (K8 kernel) and `None` for absent towers — the reference contract.
 The open_clip / BioCLIP branches of the reference (simple_clip.py:137-146) are outside the hot path
-and raise.
+and raise.  `input_type: feature` towers are `MLPEncoder`s (model/mlp.py): they have no transformer stack, so the stack-wide
+switches below (fp8 forward, fp8 dgrad, numerics, deterministic mode) pass them by.
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ from .. import ops
 from .dna_encoder import CLIBDDNAEncoder, load_pre_trained_bioscan_bert
 from .image_encoder import CLIBDImageEncoder, create_vit
 from .language_encoder import CLIBDLanguageEncoder, load_pre_trained_bert
+from .mlp import MLPEncoder
 
 F32 = torch.float32
 
@@ -145,9 +147,8 @@ class SimpleCLIP(nn.Module):
             if n not in self.FP8_TOWER_SETS["all"]:
                 raise ValueError(f"enable_fp8_forward: unknown tower {n!r}")
         self.__dict__["_fp8_towers"] = towers if isinstance(towers, str) else names
-        every = [getattr(self, n).tower().stack for n in self.FP8_TOWER_SETS["all"]
-                 if getattr(self, n) is not None and hasattr(getattr(self, n), "tower")]
-        live = [n for n in names if getattr(self, n) is not None and hasattr(getattr(self, n), "tower")]
+        every = [getattr(self, n).tower().stack for n in self.FP8_TOWER_SETS["all"] if self._has_stack(getattr(self, n))]
+        live = [n for n in names if self._has_stack(getattr(self, n))]
         stacks = [getattr(self, n).tower().stack for n in live]
         site_sel = self.FP8_TOWER_SITES.get(towers, {}) if isinstance(towers, str) else {}
         sites = [site_sel.get(n) for n in live]
@@ -186,13 +187,17 @@ class SimpleCLIP(nn.Module):
                 raise ValueError(f"enable_fp8_dgrad: unknown tower {n!r}")
         for n in self.FP8_TOWER_SETS["all"]:
             enc = getattr(self, n)
-            if enc is not None and hasattr(enc, "tower"):
+            if self._has_stack(enc):
                 enc.tower().stack.set_numerics(dgrad="fp8" if (enabled and n in names) else "bf16")
         return self
 
+    @staticmethod
+    def _has_stack(enc) -> bool:
+        """a tower over a TransformerStack; the feature towers (MLPEncoder) have a tower() and no stack: fp32-grade, one mode"""
+        return enc is not None and hasattr(enc, "tower") and hasattr(enc.tower(), "stack")
+
     def _stacks(self):
-        return [enc.tower().stack for enc in (self.image_encoder, self.dna_encoder, self.language_encoder)
-                if enc is not None and hasattr(enc, "tower")]
+        return [enc.tower().stack for enc in (self.image_encoder, self.dna_encoder, self.language_encoder) if self._has_stack(enc)]
 
     def set_numerics(self, **settings):
         """Backward arithmetic switches of every tower (clibd_amd.engine.NUMERICS_CHOICES: residual_grad = "bf16" | "fp32",
@@ -221,9 +226,11 @@ class SimpleCLIP(nn.Module):
         out = {}
         for name in ("image_encoder", "dna_encoder", "language_encoder"):
             enc = getattr(self, name)
-            if enc is not None and hasattr(enc, "tower"):
+            if self._has_stack(enc):
                 st = enc.tower().stack
                 out[name] = dict(st.numerics, forward="fp8 (e4m3) GEMM operands" if st.fp8 is not None else "bf16")
+            elif enc is not None and hasattr(enc, "tower"):
+                out[name] = {"forward": "fp32-grade (split bf16)"}
         return out
 
     def join_streams(self):
@@ -257,9 +264,9 @@ def load_clip_model(args, device=None):
     out_dim = mc.output_dim
 
     image_encoder = dna_encoder = language_encoder = None
-    if image_cfg is not None:
-        if _get(image_cfg, "input_type", "image") != "image":
-            raise NotImplementedError("pre-extracted feature (MLP) towers are out of scope (SURVEY §2 row 8)")
+    if image_cfg is not None and _get(image_cfg, "input_type", "image") != "image":
+        image_encoder = MLPEncoder(input_dim=image_cfg.input_dim, hidden_dim=image_cfg.hidden_dim, output_dim=out_dim)   # simple_clip.py:172-175
+    elif image_cfg is not None:
         vit = create_vit(_get(image_cfg, "pre_train_model", "vit_base_patch16_224"))
         # reference key (simple_clip.py:154-165): a SimCLR-style ViT checkpoint {"state_dict": ...}, DDP prefix stripped, loaded
         # STRICTLY into the timm-shaped body; `vit_checkpoint` is this package's alias for a plain local timm state dict
@@ -278,9 +285,9 @@ def load_clip_model(args, device=None):
             raise TypeError(f"Using {lang_cfg.input_type} as language input is not support yet.")
         _, bert = load_pre_trained_bert(_get(lang_cfg, "pre_train_model", "prajjwal1/bert-small"))
         language_encoder = CLIBDLanguageEncoder(model=bert, r=4, num_classes=out_dim, lora_layer=[] if disable_lora else None)
-    if dna_cfg is not None:
-        if _get(dna_cfg, "input_type", "sequence") != "sequence":
-            raise NotImplementedError("pre-extracted feature (MLP) towers are out of scope (SURVEY §2 row 8)")
+    if dna_cfg is not None and _get(dna_cfg, "input_type", "sequence") != "sequence":
+        dna_encoder = MLPEncoder(input_dim=dna_cfg.input_dim, hidden_dim=dna_cfg.hidden_dim, output_dim=out_dim)   # simple_clip.py:211-214
+    elif dna_cfg is not None:
         ckpt = _get(args, "bioscan_bert_checkpoint")
         pre = _get(mc, "pre_train_for_barcode_bert")
         if pre == "BIOSCAN-5M":

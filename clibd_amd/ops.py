@@ -1255,6 +1255,80 @@ def linear_f32_bwd(dout: torch.Tensor, x: torch.Tensor, w: torch.Tensor, need_dx
     return dx, dw, db
 
 
+# ------------------------------------------------------------------------------------------------ feature-tower linear layers (include/clibd_hip_mlp.h)
+def mlp_linear_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(x w^T + bias) at split-bf16 accuracy in one launch (clibd_mlp_linear_fwd): x fp32 [B, K], w fp32 [N, K], bias fp32 [N] or
+    None -> fp32 [B, N]; act = ReLU when `relu`.  K % 4 == 0, N % 16 == 0, both <= 4096."""
+    _chk(x, F32, "x"); _chk(w, F32, "w")
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1]:
+        raise ValueError("mlp_linear_fwd: expected x [B, K] and w [N, K]")
+    B, K = x.shape
+    N = w.shape[0]
+    if bias is not None:
+        _chk(bias, F32, "bias")
+        if bias.numel() != N:
+            raise ValueError("mlp_linear_fwd: bias must have N elements")
+    if out is None:
+        out = torch.empty((B, N), dtype=F32, device=x.device)
+    else:
+        _chk(out, F32, "out")
+        if tuple(out.shape) != (B, N):
+            raise ValueError(f"mlp_linear_fwd: out must be [{B}, {N}]")
+    check(_lib.load().clibd_mlp_linear_fwd(x.data_ptr(), w.data_ptr(), _p(bias), B, N, K, int(bool(relu)), out.data_ptr(), _stream()), "mlp_linear_fwd")
+    return out
+
+
+def mlp_linear_dgrad(dy: torch.Tensor, w: torch.Tensor, h: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(dy w) * [h > 0] in one launch (clibd_mlp_linear_dgrad): dy fp32 [B, N], w fp32 [N, K], h fp32 [B, K] = the post-ReLU activation
+    that fed this layer (None: no mask) -> dx fp32 [B, K]."""
+    _chk(dy, F32, "dy"); _chk(w, F32, "w")
+    if dy.dim() != 2 or w.dim() != 2 or w.shape[0] != dy.shape[1]:
+        raise ValueError("mlp_linear_dgrad: expected dy [B, N] and w [N, K]")
+    B, N = dy.shape
+    K = w.shape[1]
+    if h is not None:
+        _chk(h, F32, "h")
+        if tuple(h.shape) != (B, K):
+            raise ValueError(f"mlp_linear_dgrad: h must be [{B}, {K}]")
+    if out is None:
+        out = torch.empty((B, K), dtype=F32, device=dy.device)
+    else:
+        _chk(out, F32, "out")
+        if tuple(out.shape) != (B, K):
+            raise ValueError(f"mlp_linear_dgrad: out must be [{B}, {K}]")
+    check(_lib.load().clibd_mlp_linear_dgrad(dy.data_ptr(), w.data_ptr(), _p(h), B, N, K, out.data_ptr(), _stream()), "mlp_linear_dgrad")
+    return out
+
+
+def mlp_linear_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None,
+                     accumulate: bool = False, need_db: bool = True):
+    """dw [N, K] (+)= dy^T x and db [N] (+)= dy.sum(0) in one launch (clibd_mlp_linear_wgrad): dy fp32 [B, N], x fp32 [B, K].
+    dw / db: fp32 tensors to write (accumulate=True: to add to, e.g. views of the trainer's flat gradient bucket); None allocates
+    (db only when need_db).  One summation order: two calls give the same bits.  Returns (dw, db)."""
+    _chk(dy, F32, "dy"); _chk(x, F32, "x")
+    if dy.dim() != 2 or x.dim() != 2 or x.shape[0] != dy.shape[0]:
+        raise ValueError("mlp_linear_wgrad: expected dy [B, N] and x [B, K]")
+    B, N = dy.shape
+    K = x.shape[1]
+    if accumulate and (dw is None or (need_db and db is None)):
+        raise ValueError("mlp_linear_wgrad: accumulate needs the tensors to add to")
+    if dw is None:
+        dw = torch.empty((N, K), dtype=F32, device=dy.device)
+    if db is None and need_db:
+        db = torch.empty((N,), dtype=F32, device=dy.device)
+    _chk(dw, F32, "dw")
+    if tuple(dw.shape) != (N, K):
+        raise ValueError(f"mlp_linear_wgrad: dw must be [{N}, {K}]")
+    if db is not None:
+        _chk(db, F32, "db")
+        if db.numel() != N:
+            raise ValueError("mlp_linear_wgrad: db must have N elements")
+    check(_lib.load().clibd_mlp_linear_wgrad(dy.data_ptr(), x.data_ptr(), B, N, K, dw.data_ptr(), _p(db), int(bool(accumulate)), _stream()),
+          "mlp_linear_wgrad")
+    return dw, db
+
+
 _ce_err: dict = {}   # device -> the int32 error word of ce_rows_fwd (sticky: bit 0 = a target outside [0, C))
 
 

@@ -1,10 +1,12 @@
-"""The three encoder towers as autograd Functions over the HIP engine (clibd_amd.engine).
+"""The encoder towers as autograd Functions over the HIP engine (clibd_amd.engine).
 
 ViTTower      = timm vit_base_patch16_224 forward/backward + LoRA(q,v) + trainable head
                 (reference: model/image_encoder.py:49-107; timm created at model/simple_clip.py:150-153)
 BertTower     = HF BERT encoder (post-LN) + LoRA(query,value) with one of two heads:
    head="mlm"   BertForMaskedLM transform + replaced decoder, softmax(-1).mean(1)   (model/dna_encoder.py:80-137)
    head="mean"  last_hidden_state.mean(1) -> proj                                  (model/language_encoder.py:36-89)
+MLPTower      = Linear, ReLU, Linear, ReLU, Linear over pre-extracted feature rows, fp32-grade, no transformer stack
+                (reference: model/mlp.py:23-37; built at model/simple_clip.py:172-175, 211-214 for `input_type: feature`)
 """
 from __future__ import annotations
 
@@ -414,3 +416,67 @@ class BertTower(_Tower):
                     ops.batch_sum(de.view(B, S * H), grads[id(tabs[1])][:S], **_ordered(det))
                 ops.bert_embed_bwd(state["ids"].view(-1), None if state["tt"] is None else state["tt"].view(-1), de,
                                    grads.get(id(tabs[0])), grads.get(id(tabs[2])), **_ordered(det))
+
+
+# =========================================================================================================
+class MLPTower(_Tower):
+    """The reference's MLPEncoder (model/mlp.py:23-37: Linear, ReLU, Linear, ReLU, Linear) over pre-extracted feature rows, on the
+    fp32-grade linear kernels of include/clibd_hip_mlp.h: three launches forward, five backward.  No transformer stack, no weight
+    images and no atomics: every sum has one order, so the tower is always deterministic."""
+
+    MAX_DIM = 4096
+
+    def __init__(self, linears):
+        """linears: the encoder's three nn.Linear, bottom to top."""
+        self.layers = list(linears)
+        if len(self.layers) != 3 or any(l.bias is None for l in self.layers):
+            raise NotSupportedYet("MLP tower: three biased Linear layers (the reference's MLPEncoder)")
+        for i, lin in enumerate(self.layers):
+            N, K = lin.weight.shape
+            if K <= 0 or N <= 0 or K % 4 or N % 16 or K > self.MAX_DIM or N > self.MAX_DIM:
+                raise NotSupportedYet(f"MLP tower: layer {i} is {K} -> {N}; the kernels take an input width that is a positive multiple of 4, "
+                                      f"hidden and output widths that are multiples of 16, all at most {self.MAX_DIM}")
+
+    def trainable_params(self):
+        return [p for g in self.grad_groups() for p in g]
+
+    def grad_groups(self):
+        return [[lin.weight, lin.bias] for lin in reversed(self.layers)]
+
+    def invalidate_weight_images(self):
+        """nothing is cached: every launch reads the fp32 parameters"""
+
+    @property
+    def deterministic(self) -> bool:
+        return True
+
+    @deterministic.setter
+    def deterministic(self, on: bool):
+        pass   # there is no other mode to switch to
+
+    def _forward(self, inputs, save):
+        (x,) = inputs
+        l1, l2, l3 = self.layers
+        if x.dim() != 2 or x.shape[1] != l1.weight.shape[1]:
+            raise ValueError(f"feature encoder expects [B, {l1.weight.shape[1]}]")
+        x = x.detach().to(F32).contiguous()
+        h1 = ops.mlp_linear_fwd(x, _f32c(l1.weight), _f32c(l1.bias), relu=True)
+        h2 = ops.mlp_linear_fwd(h1, _f32c(l2.weight), _f32c(l2.bias), relu=True)
+        out = ops.mlp_linear_fwd(h2, _f32c(l3.weight), _f32c(l3.bias))
+        return out, ((x, h1, h2) if save else None)
+
+    def _backward(self, dout, state, grads):
+        """wgrad3, dgrad3->2 (mask h2), wgrad2, dgrad2->1 (mask h1), wgrad1; the features are data, so there is no dx.  `grads` buffers
+        are accumulated into (the trainer's flat bucket, or a zeroed GradBucket)."""
+        dy = dout
+        for i in (2, 1, 0):
+            lin, a = self.layers[i], state[i]
+            dw, db = grads.get(id(lin.weight)), grads.get(id(lin.bias))
+            if dw is not None:
+                ops.mlp_linear_wgrad(dy, a, dw, None if db is None else db.view(-1), accumulate=True, need_db=db is not None)
+            elif db is not None:
+                ops.batch_sum(dy, db.view(-1), ordered=True)
+            self._ready(2 - i)
+            if i == 0 or not any(id(p) in grads for l in self.layers[:i] for p in (l.weight, l.bias)):
+                break
+            dy = ops.mlp_linear_dgrad(dy, _f32c(lin.weight), a)
