@@ -189,8 +189,14 @@ MLP_SIGNATURES = {
     "clibd_mlp_linear_wgrad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
+# attention for 128- and 192-wide heads (include/clibd_hip_attn_wide.h): a ninth additive table, bound after the other eight
+ATTN_WIDE_SIGNATURES = {
+    "clibd_attention_wide_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
+    "clibd_attention_wide_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
+}
+
 _lib = None
-ABI_VERSION = 7   # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
+ABI_VERSION = 7  # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
 
 class ClibdHipError(RuntimeError):
@@ -213,7 +219,8 @@ def load() -> C.CDLL:
         )
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items())
-                              + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(INSECT_SIGNATURES.items()) + list(MLP_SIGNATURES.items())):
+                              + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(INSECT_SIGNATURES.items()) + list(MLP_SIGNATURES.items())
+                              + list(ATTN_WIDE_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

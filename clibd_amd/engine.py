@@ -207,11 +207,12 @@ class TransformerStack:
     """Shared machinery of the ViT (pre-LN) and BERT (post-LN) encoder stacks."""
 
     def __init__(self, layers: List[LayerSpec], hidden: int, heads: int, pre_ln: bool, eps: float):
-        if hidden != heads * 64:
-            raise NotSupportedYet(f"attention kernel is specialised for head_dim 64 (hidden={hidden}, heads={heads})")
+        if heads < 1 or hidden % heads or hidden // heads not in self.HEAD_DIMS:
+            raise NotSupportedYet(f"attention kernels are built for head_dim 64, 128 and 192 (hidden={hidden}, heads={heads})")
         if hidden % 64 or hidden > 1024:
             raise NotSupportedYet("hidden size must be a multiple of 64 and <= 1024")
         self.layers, self.H, self.heads, self.pre_ln, self.eps = layers, hidden, heads, pre_ln, eps
+        self.dh = hidden // heads   # 64: attention.hip, every form.  128 / 192: attention_wide.hip (no key mask, no class-row-only form, no e4m3 output)
         self.FF = layers[0].fc1_w.shape[0]
         self._cache: List[_LayerCache] = []
         self._cache_key = None
@@ -222,7 +223,8 @@ class TransformerStack:
         self._c2, self._c2_age = None, 0   # dgrad = "fp8" under full fine-tune: the per-layer d(fc1 out) scales and how many refreshes old they are
         self.dgrad8_sites = ("mlp", "proj")   # dgrad = "fp8": which of the covered GEMMs take it ("mlp" = the fc2 -> fc1 pair, "proj"); tools/dgrad8_sites_study.py
 
-    DGRAD8_C2_EVERY = 64   # full fine-tune: refreshes (= steps) between two host reads of the fc2 images' l1 norms
+    HEAD_DIMS = (64, 128, 192)
+    DGRAD8_C2_EVERY = 64  # full fine-tune: refreshes (= steps) between two host reads of the fc2 images' l1 norms
 
     def set_numerics(self, **settings):
         before = (self.numerics.get("ln_fold"), self.numerics.get("dgrad"))
@@ -447,6 +449,11 @@ class TransformerStack:
         """full-sequence attention into o (e4m3 with the projection's scale under the all-site fp8 forward).  Returns (o, att_sv): the
         training forward of the single-pass attention backward writes this layer's own o and saves its rounding residual and the lse."""
         o_lo = lse = None
+        if self.dh != 64:   # wide heads: the training forward saves the lse its backward starts from; the no-grad forward passes none
+            if p.save:
+                lse = torch.empty((p.B * self.heads * p.S,), dtype=F32, device=p.dev)
+            ops.attention_wide_fwd(qkv, p.B, p.S, self.heads, self.dh, o, lse=lse, drop=drop)
+            return o, (dict(lse=lse) if p.save else None)
         if p.sp_ok:
             o = o if p.keep else p.new(self.H, BF16)
             o_lo, lse = p.new(self.H, BF16), torch.empty((p.B * self.heads * p.S,), dtype=F32, device=p.dev)
@@ -503,6 +510,14 @@ class TransformerStack:
         mode = None if f8s is None else ("all" if "qkv_in" in f8s[0] else "mlp")   # "mlp": QKV / attention / projection stay bf16
         if mode == "all" and full:
             raise NotSupportedYet("fp8 forward on every site with trainable base weights (the MLP-pair selection is built)")
+        wide = self.dh != 64
+        if wide and key_mask is not None:
+            raise NotSupportedYet(f"a key mask with head_dim {self.dh}: the wide-head attention kernels take full sequences only (head_dim 64 has the masked form)")
+        if wide and cls_only_last:
+            raise NotSupportedYet(f"the class-row-only last block with head_dim {self.dh} (head_dim 64 only)")
+        if wide and mode == "all":
+            raise NotSupportedYet(f"fp8 forward on every site with head_dim {self.dh}: the wide-head attention writes no e4m3 output "
+                                  "(the MLP-pair selection, sites=('fc1_in', 'fc2_in'), is built)")
         cal = self._calib if f8s is None else None      # calibration pass: bf16 forward recording max |operand| per site
         amax = lambda t_: t_.abs().amax().float()
         AT = ops.FP8 if f8s is not None else BF16    # dtype of the GEMM-operand temporaries
@@ -519,7 +534,7 @@ class TransformerStack:
         HC = 3 * FF // 2 if gg == "e4m7" else FF                                                     # columns of that buffer
         act_save = {"bf16": ops.ACT_GELU_SAVE_GRAD, "u8": ops.ACT_GELU_SAVE_GRAD_U8, "e4m7": ops.ACT_GELU_SAVE_GRAD_E12}[gg]
         h_tmp = new(FF, BF16) if (f8s is not None and not save) else None       # the fp8 fc1 form always writes gelu'
-        sp_ok = save and key_mask is None and f8s is None and S <= 224 and self.numerics["attn_bwd"] == "sp"
+        sp_ok = save and key_mask is None and f8s is None and S <= 224 and self.numerics["attn_bwd"] == "sp" and not wide
         # norm2 -> fc1 as the algebraic fold (numerics ln_fold): pre-LN, frozen base, bf16 forward, shapes the 256x256 kernel takes
         fold = (self.pre_ln and self.numerics["ln_fold"] == "on" and self._cache[0].w1g is not None and f8s is None and not full
                 and GG == BF16 and H % 256 == 0 and FF % 256 == 0 and M >= 1024 and ((M + 255) // 256) * (H // 256) >= 128
@@ -528,7 +543,7 @@ class TransformerStack:
         if fold and h_tmp is None and not save:
             h_tmp = new(FF, BF16)   # the consumer epilogue always writes gelu' (eval forward: into a scratch buffer)
         p = SimpleNamespace(B=B, S=S, dev=dev, new=new, key_mask=key_mask, keep=keep, sp_ok=sp_ok, act_save=act_save, h_tmp=h_tmp,
-                            fold_sums=fold_sums)
+                            fold_sums=fold_sums, save=save)
         t, saved = t0, []
         for i, (L, c) in enumerate(zip(self.layers, self._cache)):
             lora = L.lora is not None
@@ -807,7 +822,9 @@ class TransformerStack:
         return dx_f32 if full else None
 
     def _attention_bwd(self, rec, dout, B, S, key_mask, dqkv, drop=None, nq=None):
-        if "lse" in rec:   # the forward saved what the single-pass kernel needs
+        if self.dh != 64:   # wide heads: one backward form, from the forward's lse (no key mask, every query row: forward() refused the rest)
+            ops.attention_wide_bwd(rec["qkv"], dout, rec["lse"], B, S, self.heads, self.dh, dqkv, drop=drop)
+        elif "lse" in rec:   # the forward saved what the single-pass kernel needs
             ops.attention_bwd_sp(rec["qkv"], dout, rec["o_att"], rec["o_lo"], rec["lse"], B, S, self.heads, dqkv, drop=drop)
         else:
             ops.attention_bwd(rec["qkv"], dout, B, S, self.heads, key_mask, dqkv, nq=nq, drop=drop)

@@ -534,6 +534,39 @@ def attention_bwd_sp(qkv, dout, out, o_lo, lse, B, S, nheads, dqkv, drop=None) -
                                              dqkv.data_ptr(), *_drop_args(drop), _stream()), "attention_bwd_sp")
 
 
+def _wide_shapes(op: str, B: int, S: int, nheads: int, head_dim: int, named) -> None:
+    H = nheads * head_dim
+    for nm, t, cols in named:
+        _chk(t, BF16, nm)
+        if tuple(t.shape) != (B * S, cols * H):
+            raise ValueError(f"{op}: {nm} must be [B*S, {cols}H] with H = nheads*head_dim = {H}")
+
+
+def attention_wide_fwd(qkv: torch.Tensor, B: int, S: int, nheads: int, head_dim: int, out: torch.Tensor, lse: Optional[torch.Tensor] = None,
+                       drop=None) -> None:
+    """Attention for 128- / 192-wide heads (clibd_attention_wide_fwd): full sequences, no key mask, bf16 out [B*S, H].
+    lse (fp32 [B*nheads*S], optional): the log2-domain log-sum-exp attention_wide_bwd needs."""
+    _wide_shapes("attention_wide_fwd", B, S, nheads, head_dim, (("qkv", qkv, 3), ("out", out, 1)))
+    if lse is not None:
+        _chk(lse, F32, "lse")
+        if lse.numel() != B * nheads * S:
+            raise ValueError("attention_wide_fwd: lse must have B*nheads*S elements")
+    check(_lib.load().clibd_attention_wide_fwd(qkv.data_ptr(), B, S, nheads, head_dim, out.data_ptr(), _p(lse), *_drop_args(drop), _stream()),
+          "attention_wide_fwd")
+
+
+def attention_wide_bwd(qkv, dout, lse, B: int, S: int, nheads: int, head_dim: int, dqkv, drop=None) -> None:
+    """dqkv [B*S, 3H] (every row, all three sections) from qkv, dout [B*S, H] and the forward's lse (clibd_attention_wide_bwd)."""
+    _wide_shapes("attention_wide_bwd", B, S, nheads, head_dim, (("qkv", qkv, 3), ("dout", dout, 1), ("dqkv", dqkv, 3)))
+    if lse is None:
+        raise ValueError("attention_wide_bwd: needs the lse the forward wrote")
+    _chk(lse, F32, "lse")
+    if lse.numel() != B * nheads * S:
+        raise ValueError("attention_wide_bwd: lse must have B*nheads*S elements")
+    check(_lib.load().clibd_attention_wide_bwd(qkv.data_ptr(), dout.data_ptr(), lse.data_ptr(), B, S, nheads, head_dim, dqkv.data_ptr(),
+                                               *_drop_args(drop), _stream()), "attention_wide_bwd")
+
+
 def lora_pack(a_q, a_v, b_q, b_v, v_fwd, v_bwd, a_cat, w_dt) -> None:
     H = a_q.shape[1]
     for nm, t, shape in (("a_q", a_q, (4, H)), ("a_v", a_v, (4, H)), ("b_q", b_q, (H, 4)), ("b_v", b_v, (H, 4))):

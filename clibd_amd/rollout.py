@@ -28,6 +28,7 @@ Stated divergences from the reference:
   * ties at the k-th smallest value, which torch.topk leaves unspecified: entries equal to it are zeroed in ascending flat index;
   * the text tower and key masks are not covered: the reference has no such rollout;
   * under the fp8 forward on every site with trainable base weights the tower's recording forward raises NotSupportedYet;
+  * a tower whose heads are not 64 wide (the newer BarcodeBERT checkpoints: 128 / 192) raises NotSupportedYet: the map kernel reads 64-wide heads;
   * no heat-map overlay and no drawing (cv2 and matplotlib are out of scope, as for the other result scripts).
 """
 from __future__ import annotations
@@ -38,6 +39,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .engine import NotSupportedYet
 
 FUSIONS = {"mean": ops.FUSE_MEAN, "max": ops.FUSE_MAX, "min": ops.FUSE_MIN}
 VIT_WINDOW = slice(1, -6)     # image_representation_visualization.py: attentions[1:-6]
@@ -112,6 +114,8 @@ def attention_rollout(encoder, inputs: torch.Tensor, head_fusion: str = "min", d
     default_window = VIT_WINDOW if kind == "vit" else DNA_WINDOW
     tower = encoder.tower()
     stack = tower.stack
+    if getattr(stack, "dh", 64) != 64:   # clibd_attn_fused_maps reads q and k at 64-column strides: it would misread a wide tower's qkv
+        raise NotSupportedYet(f"attention rollout is built for head_dim 64 (this tower: {stack.dh})")
     layers = select_layers(len(stack.layers), layer_idx, default_window if window is None else window)
     dev = next(encoder.parameters()).device
     x = inputs.to(dev)

@@ -126,6 +126,8 @@ class ViTTower(_Tower):
                                     blk.mlp.fc1.bias, blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.norm1.weight, blk.norm1.bias,
                                     blk.norm2.weight, blk.norm2.bias, lora))
         heads = getattr(vit.blocks[0].attn, "num_heads", H // 64)
+        if H != int(heads) * 64:   # the last block's class-row-only attention exists for 64-wide heads only, and no reference ViT has another width
+            raise NotSupportedYet(f"ViT tower: head_dim 64 only (hidden={H}, heads={heads}); the 128- / 192-wide attention kernels serve the BERT towers")
         self.H = H
         self.stack = TransformerStack(layers, H, heads, pre_ln=True, eps=float(vit.blocks[0].norm1.eps))
         self._patch_key, self._patch_w = None, None
@@ -314,6 +316,10 @@ class BertTower(_Tower):
         B, S = ids.shape
         if S > 256:
             raise NotSupportedYet("sequence length > 256")
+        if self.stack.dh == 192 and S > 192:   # two [S, 192] bf16 images must fit the LDS of a compute unit
+            raise NotSupportedYet("sequence length > 192 with head_dim 192")
+        if self.stack.dh != 64 and attn_mask is not None:
+            raise NotSupportedYet(f"an attention mask with head_dim {self.stack.dh}: the wide-head attention kernels take full sequences only")
         H = self.H
         dev = ids.device
         full = save and self._full()
