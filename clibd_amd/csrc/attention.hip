@@ -1,101 +1,21 @@
 // Multi-head attention forward / backward for short sequences (S <= 256, head dim 64) on gfx950.
 //
-// One workgroup (4 waves) per (batch, head).  The whole K/V (forward) or K,V then Q,dO (backward) of that
-// head lives in LDS as [S_pad][64] bf16 tiles (128-B rows, 16-B chunk index XOR (row&7)), filled by 16-byte
-// LDS-DMA with the swizzle applied on the per-lane source address.  Scores for one 16-query tile against
-// ALL keys fit in registers (<= 16 key tiles x 4 fp32), so softmax is an exact full-row softmax: no online
-// rescaling, no saved LSE.
-//
-// Orientation ("key on the MFMA row, query on the lane"): S^T = K·Q^T via
-// v_mfma_f32_16x16x32_bf16(A = K rows, B = Q rows) leaves each lane with ONE query (lane&15) and keys
-// 16*kt + 4*(lane>>4) + reg.  Those accumulators, packed to bf16, are directly the B operand of the next
-// product that contracts over keys (P·V, dS·K) with the k-slot -> key map
-//      kappa(g, j) = 32*s + 16*(j>>2) + 4*g + (j&3)        (g = lane>>4, j = 0..7)
-// and the other operand (V^T / K^T rows = head-dim) is fetched with ds_read_b64_tr_b16 using the same map.
-#include "common.h"
+// One workgroup (4 waves) per (batch, head).  The whole K/V (forward) or K,V then Q,dO (backward) of that head lives in LDS as [S_pad][64] bf16
+// images.  The image layout, its LDS-DMA staging, the fragment reads, the orientation ("key on the MFMA row, query on the lane") with its
+// k-slot -> key map kappa, the 16-byte row store and NEG_BIG are in attn_image.h, shared with attention_wide.hip and rollout.hip.
+// Scores for one 16-query tile against ALL keys fit in registers (<= 16 key tiles x 4 fp32), so softmax is an exact full-row softmax: no
+// online rescaling, no saved LSE.
+#include "attn_image.h"
 #include "../../include/clibd_hip.h"
-#include "host_util.h"
 #include <stdlib.h>
 
 namespace clibd {
-
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int ATT_THREADS = 256;
 constexpr int ATT_WAVES = 4;
 constexpr int DH = 64;
 constexpr int MAX_KT = 16;  // S_pad <= 256
 
-__device__ __forceinline__ int tile_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-
-// stage rows [0,S_pad) x 64 bf16 of one head (global row stride `ld` elements) into an LDS tile
-__device__ __forceinline__ void stage_head_tile(char* lds_tile, const unsigned short* gbase, size_t ld, int S, int S_pad,
-                                                int wave, int lane, int nwaves = ATT_WAVES) {
-    const int prow = lane >> 3;
-    const int chunk = (lane & 7) ^ prow;
-    for (int p = wave; p < (S_pad >> 3); p += nwaves) {
-        const int row = min(p * 8 + prow, S - 1);
-        glds16(gbase + (size_t)row * ld + chunk * 8, lds_tile + p * 1024);
-    }
-}
-
-__device__ __forceinline__ bf16x8 lds_row_frag(const char* tile, int row, int ks, int g) {
-    return *(const bf16x8*)(tile + tile_off(row, 4 * ks + g));
-}
-
-// transposed fragment: rows d = 16*dt + (lane&15), k-slots (g,j) -> tile rows kappa(g,j) = 32*s+16*(j>>2)+4*g+(j&3)
-__device__ __forceinline__ bf16x8 lds_tr_frag(const char* tile, int s, int dt, int lane) {
-    const int g = lane >> 4, i = lane & 15;
-    const int q = i >> 2, p = i & 3;
-    const int r0 = 32 * s + 4 * g + q;
-    const int ch = 2 * dt + (p >> 1);
-    const int a0 = tile_off(r0, ch) + 8 * (p & 1);
-    const int a1 = tile_off(r0 + 16, ch) + 8 * (p & 1);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(tile + a0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(tile + a1));
-    return (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-__device__ __forceinline__ bf16x8 pack_frag(const f32x4& a, const f32x4& b) {
-    bf16x8 r;
-    r[0] = (short)f2bf(a[0]); r[1] = (short)f2bf(a[1]); r[2] = (short)f2bf(a[2]); r[3] = (short)f2bf(a[3]);
-    r[4] = (short)f2bf(b[0]); r[5] = (short)f2bf(b[1]); r[6] = (short)f2bf(b[2]); r[7] = (short)f2bf(b[3]);
-    return r;
-}
-
-// across the 4 lane groups (lane>>4) at fixed lane&15: v_permlane swaps, not ds_bpermute (common.h)
-__device__ __forceinline__ float group4_sum(float v) { return rows4_sum(v); }
-__device__ __forceinline__ float group4_max(float v) { return rows4_max(v); }
-
-// One 16-row x 64-column output tile of a wave: lane (i = lane & 15, g = lane >> 4) holds v[dt][r] = element (row i, column
-// 16 dt + 4 g + r) — 8 bytes per (lane, dt).  Written that way (four dwordx2 per lane) a store instruction covers 32-byte pieces
-// and the output tail of the attention kernels is store-issue bound.  A v_permlane16_swap between the lane rows g and g ^ 1 (a
-// 2 x 2 transpose of the (dt, dt + 1) chunks) leaves every lane 16 contiguous bytes, and each of the TWO dwordx4 stores of a tile
-// then covers 64 contiguous bytes of all 16 rows.  Every lane must call this (the swap is a full-wave operation); `on` guards
-// the stores only (it is a function of the row, identical in the lanes that exchange).  Values, and so results, are unchanged.
-__device__ __forceinline__ void permlane16_swap_u32(unsigned& a, unsigned& b) {
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ void store_rows16(unsigned short* row, const f32x4 (&v)[4], float mul, bool on, int g) {
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr) {
-        unsigned a0 = pack2bf(v[2 * pr][0] * mul, v[2 * pr][1] * mul), a1 = pack2bf(v[2 * pr][2] * mul, v[2 * pr][3] * mul);
-        unsigned b0 = pack2bf(v[2 * pr + 1][0] * mul, v[2 * pr + 1][1] * mul), b1 = pack2bf(v[2 * pr + 1][2] * mul, v[2 * pr + 1][3] * mul);
-        permlane16_swap_u32(a0, b0);   // even g: (a, b) = columns 4g .. 4g+7 of tile dt = 2 pr;  odd g: columns 4(g-1) .. 4(g-1)+7 of dt = 2 pr + 1
-        permlane16_swap_u32(a1, b1);
-        if (on) *(uint4*)(row + 16 * (2 * pr + (g & 1)) + 8 * (g >> 1)) = make_uint4(a0, a1, b0, b1);
-    }
-}
-
-// the (dt, dt + 1) = (2 pr, 2 pr + 1) half of store_rows16, for a wave that holds only those two column tiles
-__device__ __forceinline__ void store_rows16_pair(unsigned short* row, const f32x4& va, const f32x4& vb, float mul, bool on, int g, int pr) {
-    unsigned a0 = pack2bf(va[0] * mul, va[1] * mul), a1 = pack2bf(va[2] * mul, va[3] * mul);
-    unsigned b0 = pack2bf(vb[0] * mul, vb[1] * mul), b1 = pack2bf(vb[2] * mul, vb[3] * mul);
-    permlane16_swap_u32(a0, b0);
-    permlane16_swap_u32(a1, b1);
-    if (on) *(uint4*)(row + 16 * (2 * pr + (g & 1)) + 8 * (g >> 1)) = make_uint4(a0, a1, b0, b1);
-}
 // Training forward (single-pass backward, attention_bwd_sp_kernel): beside out = bf16(o * mul) also the bf16 residual of that
 // rounding, o_lo = bf16(o * mul - float(bf16(o * mul))), so that the backward can take delta = dO . (o_hi + o_lo) with fp32-class
 // accuracy (delta from the bf16 output alone costs the q-adapter gradients 4-7 %: DESIGN.md §3.2).
@@ -108,13 +28,9 @@ __device__ __forceinline__ void store_rows16_lo(unsigned short* row_lo, const f3
             const float x = v[dt][r] * mul;
             lo[dt][r] = x - bfround(x);
         }
-    store_rows16(row_lo, lo, 1.0f, on, g);
+    store_rows<4>(row_lo, lo, 1.0f, on, g);
 }
 
-// A power of two: NEG_BIG * c2 is then exact in fp32, so a row whose keys are ALL masked has fma(NEG_BIG, c2, -(NEG_BIG * c2)) = 0 and
-// every probability exp2(0) = 1 (uniform weight, finite results).  With -1.0e30f the product rounds, the fused multiply-add returns the
-// rounding error (8e20), exp2 of it is +inf and the row leaves as NaN.  For every other row nothing changes: a masked score still underflows to 0.
-constexpr float NEG_BIG = -0x1p100f;
 
 #ifdef CLIBD_GEMM_DIAG
 // diagnostic build only (python -m clibd_amd.build --diag; tools/att_stamps.py): s_memtime at the phase boundaries of the backward
@@ -222,8 +138,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) qf[ks] = *(const bf16x8*)(qbase + (size_t)qc0 * ld + 32 * ks + 8 * g);
     }
-    stage_head_tile(kt_lds, qbase + H, ld, S, IMG, wave, lane, NW);
-    stage_head_tile(vt_lds, qbase + 2 * H, ld, S, IMG, wave, lane, NW);
+    img_stage<DH>(kt_lds, qbase + H, ld, S, IMG, wave, lane, NW);
+    img_stage<DH>(vt_lds, qbase + 2 * H, ld, S, IMG, wave, lane, NW);
     if constexpr (IMG < S_pad) {
         for (int r = threadIdx.x; r < (S_pad - IMG) * 8; r += 64 * NW) *(uint4*)(vt_lds + IMG * 128 + 16 * r) = make_uint4(0u, 0u, 0u, 0u);
     }
@@ -250,7 +166,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
                 if (kt < NKT - 1 || last_live) {
 #pragma unroll
                     for (int ks = 0; ks < 2; ++ks) {
-                        const bf16x8 kfr = lds_row_frag(kt_lds, kt * 16 + i, ks, g);
+                        const bf16x8 kfr = img_row_frag<DH>(kt_lds, kt * 16 + i, ks, g);
                         sc[0][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, qf2[0][ks], sc[0][kt], 0, 0, 0);
                         sc[1][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, qf2[1][ks], sc[1][kt], 0, 0, 0);
                     }
@@ -279,7 +195,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
 #pragma unroll
                     for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[t][kt][r]);
                 }
-                mx = group4_max(mx);
+                mx = rows4_max(mx);
                 const float mc = mx * c2;
                 float sum = 0.f;
 #pragma unroll
@@ -292,7 +208,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
                         sum += e;
                     }
                 }
-                sum = group4_sum(sum);
+                sum = rows4_sum(sum);
                 inv[t] = 1.0f / sum;
                 if (lse != nullptr && g == 0) {
                     const int qq = (2 * p + t) * 16 + i;
@@ -324,7 +240,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
                 }
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
-                    const bf16x8 vtr = lds_tr_frag(vt_lds, s, dt, lane);
+                    const bf16x8 vtr = img_tr_frag<DH>(vt_lds, s, dt, lane);
                     o[0][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vtr, pf[0], o[0][dt], 0, 0, 0);
                     o[1][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vtr, pf[1], o[1][dt], 0, 0, 0);
                 }
@@ -342,7 +258,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
                             *(unsigned*)(orow8 + 16 * dt + 4 * g) = pack4fp8(o[t][dt][0] * sc8, o[t][dt][1] * sc8, o[t][dt][2] * sc8, o[t][dt][3] * sc8);
                     }
                 } else {
-                    store_rows16(out + oidx, o[t], inv[t], q < nq, g);
+                    store_rows<4>(out + oidx, o[t], inv[t], q < nq, g);
                     if (o_lo != nullptr) store_rows16_lo(o_lo + oidx, o[t], inv[t], q < nq, g);
                 }
             }
@@ -359,7 +275,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
             if (kt == NKT - 1 && !last_live) continue;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row_frag(kt_lds, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
+                sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(kt_lds, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
             if constexpr (MASK) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sc[kt][r] = masked_score(sc[kt][r], live, 4 * kt + r);
@@ -385,7 +301,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
 #pragma unroll
             for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[kt][r]);
         }
-        mx = group4_max(mx);
+        mx = rows4_max(mx);
         const float mc = mx * c2;
         float sum = 0.f;
 #pragma unroll
@@ -398,7 +314,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
                 sum += e;
             }
         }
-        sum = group4_sum(sum);
+        sum = rows4_sum(sum);
         const float inv = 1.0f / sum;
         if (lse != nullptr && g == 0 && q < nq) lse[(size_t)blockIdx.x * S + q] = mc + __builtin_amdgcn_logf(sum);
         f32x4 o[4];
@@ -419,7 +335,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
             const bf16x8 pf = pack_frag(sc[2 * s], sc[2 * s + 1]);  // un-normalised probabilities (<= 1/(1-p)); 1/sum is applied to O
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_tr_frag(vt_lds, s, dt, lane), pf, o[dt], 0, 0, 0);
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(vt_lds, s, dt, lane), pf, o[dt], 0, 0, 0);
         }
         {
             const size_t oidx = ((size_t)b * out_seq + min(q, nq - 1)) * H + h * DH;
@@ -432,7 +348,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 3 ? 3 : 2)) void attention_fwd_kern
                         *(unsigned*)(orow8 + 16 * dt + 4 * g) = pack4fp8(o[dt][0] * sc8, o[dt][1] * sc8, o[dt][2] * sc8, o[dt][3] * sc8);
                 }
             } else {
-                store_rows16(out + oidx, o, inv, q < nq, g);
+                store_rows<4>(out + oidx, o, inv, q < nq, g);
                 if (o_lo != nullptr) store_rows16_lo(o_lo + oidx, o, inv, q < nq, g);
             }
         }
@@ -473,8 +389,8 @@ __global__ __launch_bounds__(64 * ATTP_WAVES) void attention_fwd_persistent_kern
     auto head_base = [&](int head) { return qkv + (size_t)(head / nheads) * S * ld + (size_t)(head % nheads) * DH; };
     auto stage = [&](int head, char* buf) {
         const unsigned short* qb = head_base(head);
-        stage_head_tile(buf, qb + H, ld, S, S_pad, wave, lane, ATTP_WAVES);
-        stage_head_tile(buf + S_pad * 128, qb + 2 * H, ld, S, S_pad, wave, lane, ATTP_WAVES);
+        img_stage<DH>(buf, qb + H, ld, S, S_pad, wave, lane, ATTP_WAVES);
+        img_stage<DH>(buf + S_pad * 128, qb + 2 * H, ld, S, S_pad, wave, lane, ATTP_WAVES);
     };
 
     int head = blockIdx.x;
@@ -522,7 +438,7 @@ __global__ __launch_bounds__(64 * ATTP_WAVES) void attention_fwd_persistent_kern
                 if (kt == NKT - 1 && !last_live) continue;
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
-                    sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row_frag(kt_lds, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
+                    sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(kt_lds, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
                 if constexpr (MASK) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) sc[kt][r] = masked_score(sc[kt][r], live, 4 * kt + r);
@@ -543,7 +459,7 @@ __global__ __launch_bounds__(64 * ATTP_WAVES) void attention_fwd_persistent_kern
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[kt][r]);
             }
-            mx = group4_max(mx);
+            mx = rows4_max(mx);
             const float mc = mx * c2;
             float sum = 0.f;
 #pragma unroll
@@ -556,7 +472,7 @@ __global__ __launch_bounds__(64 * ATTP_WAVES) void attention_fwd_persistent_kern
                     sum += e;
                 }
             }
-            sum = group4_sum(sum);
+            sum = rows4_sum(sum);
             const float inv = 1.0f / sum;
             if (lse != nullptr && g == 0 && q < nq) lse[(size_t)head * S + q] = mc + __builtin_amdgcn_logf(sum);
             f32x4 o[4];
@@ -577,7 +493,7 @@ __global__ __launch_bounds__(64 * ATTP_WAVES) void attention_fwd_persistent_kern
                 const bf16x8 pf = pack_frag(sc[2 * s], sc[2 * s + 1]);  // un-normalised probabilities (<= 1/(1-p)); 1/sum is applied to O
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt)
-                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_tr_frag(vt_lds, s, dt, lane), pf, o[dt], 0, 0, 0);
+                    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(vt_lds, s, dt, lane), pf, o[dt], 0, 0, 0);
             }
             {
                 const size_t oidx = ((size_t)b * out_seq + min(q, nq - 1)) * H + h * DH;
@@ -590,7 +506,7 @@ __global__ __launch_bounds__(64 * ATTP_WAVES) void attention_fwd_persistent_kern
                             *(unsigned*)(orow8 + 16 * dt + 4 * g) = pack4fp8(o[dt][0] * sc8, o[dt][1] * sc8, o[dt][2] * sc8, o[dt][3] * sc8);
                     }
                 } else {
-                    store_rows16(out + oidx, o, inv, q < nq, g);
+                    store_rows<4>(out + oidx, o, inv, q < nq, g);
                     if (o_lo != nullptr) store_rows16_lo(o_lo + oidx, o, inv, q < nq, g);
                 }
             }
@@ -665,8 +581,8 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
         }
     }
     ATT_STAMP(0);
-    stage_head_tile(t0, qbase + H, ld, S, IMG, wave, lane, NW);
-    stage_head_tile(t1, qbase + 2 * H, ld, S, IMG, wave, lane, NW);
+    img_stage<DH>(t0, qbase + H, ld, S, IMG, wave, lane, NW);
+    img_stage<DH>(t1, qbase + 2 * H, ld, S, IMG, wave, lane, NW);
     for (int r = threadIdx.x; r < S_pad; r += 64 * NW) { st_m[r] = -NEG_BIG; st_d[r] = 0.f; }
     if constexpr (PADB > 0) {
         for (int r = threadIdx.x; r < PADB / 16; r += 64 * NW) *(uint4*)(t1 + IMG * 128 + 16 * r) = make_uint4(0u, 0u, 0u, 0u);
@@ -705,8 +621,8 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
             if (kt == NKT - 1 && !last_live) continue;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row_frag(t0, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
-                dp[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row_frag(t1, kt * 16 + i, ks, g), dof[ks], dp[kt], 0, 0, 0);
+                sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(t0, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
+                dp[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(t1, kt * 16 + i, ks, g), dof[ks], dp[kt], 0, 0, 0);
             }
             if constexpr (MASK) {
 #pragma unroll
@@ -747,7 +663,7 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
 #pragma unroll
             for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[kt][r]);
         }
-        mx = group4_max(mx);
+        mx = rows4_max(mx);
         const float mc = mx * c2;
         float sum = 0.f, dl = 0.f;
 #pragma unroll
@@ -761,8 +677,8 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
                 dl += e * dp[kt][r];
             }
         }
-        sum = group4_sum(sum);
-        dl = group4_sum(dl);
+        sum = rows4_sum(sum);
+        dl = rows4_sum(dl);
         const float inv = 1.0f / sum;
         dl *= inv;                                   // delta = sum_k P dP with P = e / sum (the fp32 softmax output)
         // dS = P (dP - delta) scale = e (dP - delta) (scale / sum): the per-query factor scale / sum is applied to the dQ
@@ -783,11 +699,11 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
             const bf16x8 dsf = pack_frag(d0, d1);
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
-                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_tr_frag(t0, s, dt, lane), dsf, dq[dt], 0, 0, 0);
+                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(t0, s, dt, lane), dsf, dq[dt], 0, 0, 0);
         }
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) dq[dt] *= sinv;
-        store_rows16(dqbase + (size_t)min(q, S - 1) * ld, dq, 1.0f, q < S, g);
+        store_rows<4>(dqbase + (size_t)min(q, S - 1) * ld, dq, 1.0f, q < S, g);
     }
     ATT_STAMP(2);
     __syncthreads();  // every wave is done reading K/V tiles; statistics are visible
@@ -811,16 +727,16 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
                 const int kr = min((2 * (wave + ATT_WAVES * pi) + j) * 16 + i, S_pad - 1);   // rows S .. S_pad-1 are copies of row S-1 (never stored)
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    kfs[pi][j][ks] = lds_row_frag(t0, kr, ks, g);
-                    vfs[pi][j][ks] = lds_row_frag(t1, kr, ks, g);
+                    kfs[pi][j][ks] = img_row_frag<DH>(t0, kr, ks, g);
+                    vfs[pi][j][ks] = img_row_frag<DH>(t1, kr, ks, g);
                 }
             }
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();  // every wave holds its fragments: the images may be overwritten
-    stage_head_tile(t0, qbase, ld, S, S_pad, wave, lane);
-    stage_head_tile(t1, dobase, (size_t)H, nq, S_pad, wave, lane);  // rows >= nq are clamped copies, masked below
+    img_stage<DH>(t0, qbase, ld, S, S_pad, wave, lane, ATT_WAVES);
+    img_stage<DH>(t1, dobase, (size_t)H, nq, S_pad, wave, lane, ATT_WAVES);  // rows >= nq are clamped copies, masked below
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     ATT_STAMP(4);
@@ -857,8 +773,8 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
                 if (hq == 1 && !q1) continue;
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    qr[hq][ks] = lds_row_frag(t0, (2 * s + hq) * 16 + i, ks, g);
-                    dor[hq][ks] = lds_row_frag(t1, (2 * s + hq) * 16 + i, ks, g);
+                    qr[hq][ks] = img_row_frag<DH>(t0, (2 * s + hq) * 16 + i, ks, g);
+                    dor[hq][ks] = img_row_frag<DH>(t1, (2 * s + hq) * 16 + i, ks, g);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -903,8 +819,8 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
             }
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                const bf16x8 trdo = lds_tr_frag(t1, s, dt, lane);
-                const bf16x8 trq = lds_tr_frag(t0, s, dt, lane);
+                const bf16x8 trdo = img_tr_frag<DH>(t1, s, dt, lane);
+                const bf16x8 trq = img_tr_frag<DH>(t0, s, dt, lane);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     if (j == 1 && !live1) continue;
@@ -917,8 +833,8 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
         for (int j = 0; j < 2; ++j) {
             {
                 const size_t roff = (size_t)min(keyv[j], S - 1) * ld;
-                store_rows16(dqbase + H + roff, dk[j], scale, keyv[j] < S, g);
-                store_rows16(dqbase + 2 * H + roff, dv[j], 1.0f, keyv[j] < S, g);
+                store_rows<4>(dqbase + H + roff, dk[j], scale, keyv[j] < S, g);
+                store_rows<4>(dqbase + 2 * H + roff, dv[j], 1.0f, keyv[j] < S, g);
             }
         }
     }
@@ -926,16 +842,6 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
     } else {
     // ---------------- phase 2: per 16-key tile: dV, dK (query on the MFMA row, key on the lane) ----------------
     bf16x8 kf[2], vf[2], kfn[2], vfn[2];
-#ifdef CLIBD_ATT_NO_REFETCH
-    // TIMING-ONLY variant (tools/build_variant.sh, wrong results): the upper bound of removing this kernel's SECOND fetch of q, k, v and
-    // dO — phase 2 takes its K / V fragments from the LDS images and sweeps the K / V images as if they were Q / dO (no re-staging)
-    {
-        const int kc0 = min(wave * 16 + i, IMG - 1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) { kf[ks] = lds_row_frag(t0, kc0, ks, g); vf[ks] = lds_row_frag(t1, kc0, ks, g); }
-    }
-    __syncthreads();
-#else
     {
         const int kc0 = min(wave * 16 + i, S - 1);
 #pragma unroll
@@ -944,29 +850,22 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
             vf[ks] = *(const bf16x8*)(qbase + 2 * H + (size_t)kc0 * ld + 32 * ks + 8 * g);
         }
     }
-    stage_head_tile(t0, qbase, ld, S, IMG, wave, lane, NW);
-    stage_head_tile(t1, dobase, (size_t)H, nq, IMG, wave, lane, NW);  // rows >= nq are clamped copies, masked below
+    img_stage<DH>(t0, qbase, ld, S, IMG, wave, lane, NW);
+    img_stage<DH>(t1, dobase, (size_t)H, nq, IMG, wave, lane, NW);  // rows >= nq are clamped copies, masked below
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-#endif
 
     const int nkt = (S + 15) >> 4;
     for (int kt = wave; kt < nkt; kt += NW) {
         const int key = kt * 16 + i;
         const bool key_ok = key_live<MASK>(key_mask, b, S, key);
         {   // next key tile's K / V fragments fly during this tile's sweep over the queries
-#ifdef CLIBD_ATT_NO_REFETCH
-            const int kn = min((kt + NW) * 16 + i, IMG - 1);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) { kfn[ks] = lds_row_frag(t0, kn, ks, g); vfn[ks] = lds_row_frag(t1, kn, ks, g); }
-#else
             const int kn = min((kt + NW) * 16 + i, S - 1);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 kfn[ks] = *(const bf16x8*)(qbase + H + (size_t)kn * ld + 32 * ks + 8 * g);
                 vfn[ks] = *(const bf16x8*)(qbase + 2 * H + (size_t)kn * ld + 32 * ks + 8 * g);
             }
-#endif
         }
         f32x4 dv[4], dk[4];
 #pragma unroll
@@ -984,8 +883,8 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
                 f32x4 sv = (f32x4){0, 0, 0, 0}, dpv = (f32x4){0, 0, 0, 0};
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row_frag(t0, qt * 16 + i, ks, g), kf[ks], sv, 0, 0, 0);
-                    dpv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_row_frag(t1, qt * 16 + i, ks, g), vf[ks], dpv, 0, 0, 0);
+                    sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(t0, qt * 16 + i, ks, g), kf[ks], sv, 0, 0, 0);
+                    dpv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(t1, qt * 16 + i, ks, g), vf[ks], dpv, 0, 0, 0);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -1004,14 +903,14 @@ __global__ __launch_bounds__(64 * NW, att_bwd_min_waves(NKT, MASK, NW, DROP)) vo
             const bf16x8 dsf = pack_frag(dd[0], dd[1]);
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_tr_frag(t1, s, dt, lane), pf, dv[dt], 0, 0, 0);
-                dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_tr_frag(t0, s, dt, lane), dsf, dk[dt], 0, 0, 0);
+                dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(t1, s, dt, lane), pf, dv[dt], 0, 0, 0);
+                dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(t0, s, dt, lane), dsf, dk[dt], 0, 0, 0);
             }
         }
         {
             const size_t roff = (size_t)min(key, S - 1) * ld;
-            store_rows16(dqbase + H + roff, dk, scale, key < S, g);
-            store_rows16(dqbase + 2 * H + roff, dv, 1.0f, key < S, g);
+            store_rows<4>(dqbase + H + roff, dk, scale, key < S, g);
+            store_rows<4>(dqbase + 2 * H + roff, dv, 1.0f, key < S, g);
         }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) { kf[ks] = kfn[ks]; vf[ks] = vfn[ks]; }
@@ -1087,10 +986,10 @@ __global__ __launch_bounds__(64 * ATTB_WAVES) void attention_bwd_sp_kernel(const
             lse_r[ps] = lse[(size_t)blockIdx.x * S + row];
         }
     }
-    stage_head_tile(kimg, qbase + H, ld, S, R, wave, lane, ATTB_WAVES);
-    stage_head_tile(vimg, qbase + 2 * H, ld, S, R, wave, lane, ATTB_WAVES);
-    stage_head_tile(qimg, qbase, ld, S, R, wave, lane, ATTB_WAVES);
-    stage_head_tile(doimg, dobase, (size_t)H, S, R, wave, lane, ATTB_WAVES);
+    img_stage<DH>(kimg, qbase + H, ld, S, R, wave, lane, ATTB_WAVES);
+    img_stage<DH>(vimg, qbase + 2 * H, ld, S, R, wave, lane, ATTB_WAVES);
+    img_stage<DH>(qimg, qbase, ld, S, R, wave, lane, ATTB_WAVES);
+    img_stage<DH>(doimg, dobase, (size_t)H, S, R, wave, lane, ATTB_WAVES);
 #pragma unroll
     for (int ps = 0; ps < DPASS; ++ps) {
         const int row = 64 * ps + (int)(threadIdx.x >> 3), sub = threadIdx.x & 7;
@@ -1122,8 +1021,8 @@ __global__ __launch_bounds__(64 * ATTB_WAVES) void attention_bwd_sp_kernel(const
         keyv[j] = (wave + ATTB_WAVES * j) * 16 + i;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            kf[j][ks] = lds_row_frag(kimg, kt * 16 + i, ks, g);
-            vf[j][ks] = lds_row_frag(vimg, kt * 16 + i, ks, g);
+            kf[j][ks] = img_row_frag<DH>(kimg, kt * 16 + i, ks, g);
+            vf[j][ks] = img_row_frag<DH>(vimg, kt * 16 + i, ks, g);
         }
     }
     f32x4 dv[2][4], dk[2][4];
@@ -1147,8 +1046,8 @@ __global__ __launch_bounds__(64 * ATTB_WAVES) void attention_bwd_sp_kernel(const
                 for (int hq = 0; hq < 2; ++hq) {
 #pragma unroll
                     for (int ks = 0; ks < 2; ++ks) {
-                        qr[hq][ks] = lds_row_frag(qimg, (2 * s + hq) * 16 + i, ks, g);
-                        dor[hq][ks] = lds_row_frag(doimg, (2 * s + hq) * 16 + i, ks, g);
+                        qr[hq][ks] = img_row_frag<DH>(qimg, (2 * s + hq) * 16 + i, ks, g);
+                        dor[hq][ks] = img_row_frag<DH>(doimg, (2 * s + hq) * 16 + i, ks, g);
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -1194,13 +1093,13 @@ __global__ __launch_bounds__(64 * ATTB_WAVES) void attention_bwd_sp_kernel(const
                     // exchange image: row = key, columns 32 p + 16 hq + 4 g .. + 3 of the block (8 bytes per query tile)
                     const uint4 w4 = __builtin_bit_cast(uint4, dsf[j]);
                     const int krow = (wave + ATTB_WAVES * j) * 16 + i;
-                    *(uint2*)(dsimg + tile_off(krow, 4 * p + (g >> 1)) + 8 * (g & 1)) = make_uint2(w4.x, w4.y);
-                    *(uint2*)(dsimg + tile_off(krow, 4 * p + 2 + (g >> 1)) + 8 * (g & 1)) = make_uint2(w4.z, w4.w);
+                    *(uint2*)(dsimg + img_off<DH>(krow, 4 * p + (g >> 1)) + 8 * (g & 1)) = make_uint2(w4.x, w4.y);
+                    *(uint2*)(dsimg + img_off<DH>(krow, 4 * p + 2 + (g >> 1)) + 8 * (g & 1)) = make_uint2(w4.z, w4.w);
                 }
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
-                    const bf16x8 trdo = lds_tr_frag(doimg, s, dt, lane);
-                    const bf16x8 trq = lds_tr_frag(qimg, s, dt, lane);
+                    const bf16x8 trdo = img_tr_frag<DH>(doimg, s, dt, lane);
+                    const bf16x8 trq = img_tr_frag<DH>(qimg, s, dt, lane);
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
                         if (j >= nown) continue;
@@ -1226,20 +1125,20 @@ __global__ __launch_bounds__(64 * ATTB_WAVES) void attention_bwd_sp_kernel(const
                     // fully unrolled, the reads of the later k-slots fly under the earlier products
 #pragma unroll
                     for (int sp = 0; sp < NPT; ++sp) {
-                        const bf16x8 dsb = lds_tr_frag(dsimg, sp, qtl, lane);
-                        dq0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_tr_frag(kimg, sp, 2 * pr2, lane), dsb, dq0, 0, 0, 0);
-                        dq1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_tr_frag(kimg, sp, 2 * pr2 + 1, lane), dsb, dq1, 0, 0, 0);
+                        const bf16x8 dsb = img_tr_frag<DH>(dsimg, sp, qtl, lane);
+                        dq0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(kimg, sp, 2 * pr2, lane), dsb, dq0, 0, 0, 0);
+                        dq1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(kimg, sp, 2 * pr2 + 1, lane), dsb, dq1, 0, 0, 0);
                     }
                 } else {
 #pragma unroll 1
                     for (int sp = 0; sp < NP; ++sp) {
-                        const bf16x8 dsb = lds_tr_frag(dsimg, sp, qtl, lane);
-                        dq0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_tr_frag(kimg, sp, 2 * pr2, lane), dsb, dq0, 0, 0, 0);
-                        dq1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds_tr_frag(kimg, sp, 2 * pr2 + 1, lane), dsb, dq1, 0, 0, 0);
+                        const bf16x8 dsb = img_tr_frag<DH>(dsimg, sp, qtl, lane);
+                        dq0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(kimg, sp, 2 * pr2, lane), dsb, dq0, 0, 0, 0);
+                        dq1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(kimg, sp, 2 * pr2 + 1, lane), dsb, dq1, 0, 0, 0);
                     }
                 }
                 const int q = qt * 16 + i;
-                store_rows16_pair(dqbase + (size_t)min(q, S - 1) * ld, dq0, dq1, scale, q < S, g, pr2);
+                store_rows_pair(dqbase + (size_t)min(q, S - 1) * ld, dq0, dq1, scale, q < S, g, pr2);
             }
         }
         if (it < 4) SP_STAMP(4 + 3 * it);
@@ -1250,8 +1149,8 @@ __global__ __launch_bounds__(64 * ATTB_WAVES) void attention_bwd_sp_kernel(const
     for (int j = 0; j < 2; ++j) {
         if (j >= nown) continue;
         const size_t roff = (size_t)min(keyv[j], S - 1) * ld;
-        store_rows16(dqbase + H + roff, dk[j], scale, keyv[j] < S, g);
-        store_rows16(dqbase + 2 * H + roff, dv[j], 1.0f, keyv[j] < S, g);
+        store_rows<4>(dqbase + H + roff, dk[j], scale, keyv[j] < S, g);
+        store_rows<4>(dqbase + 2 * H + roff, dv[j], 1.0f, keyv[j] < S, g);
     }
     SP_STAMP(15);
 }
@@ -1270,12 +1169,6 @@ static int att_check(const void* qkv, int B, int S, int nheads, const char* who)
 
 using namespace clibd;
 
-#ifndef CLIBD_ATT_BWD_S256_DROP_ONE_TILE
-#define CLIBD_ATT_BWD_S256_DROP_ONE_TILE 0
-#endif
-#ifndef CLIBD_ATT_FWD_PERSISTENT_SPILLING
-#define CLIBD_ATT_FWD_PERSISTENT_SPILLING 1
-#endif
 #define ATT_DISPATCH(NKT_EXPR, MACRO) \
     switch (NKT_EXPR) {               \
         case 2: MACRO(2); break;      \
@@ -1293,8 +1186,7 @@ using namespace clibd;
 extern "C" int clibd_attention_fwd(const void* qkv, int B, int S, int nheads, const int32_t* key_mask, void* out, int nq, int out_seq,
                                    uint32_t drop_seed, int drop_thr16, float drop_scale, float out_fp8_scale, float* lse, void* o_lo,
                                    void* stream) {
-    if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "attention_fwd: bad dropout threshold");
-    if (drop_thr16 > 0 && (unsigned long long)B * nheads * S * 256ull >= (1ull << 32)) return set_error(CLIBD_EINVAL, "attention_fwd: dropout index overflow");
+    if (int e = check_dropout_args("attention_fwd", B, S, nheads, drop_thr16)) return e;
     if (int e = att_check(qkv, B, S, nheads, "fwd")) return e;
     if (!out) return set_error(CLIBD_EINVAL, "attention_fwd: null out");
     if (nq < 1 || nq > S || out_seq < nq) return set_error(CLIBD_EINVAL, "attention_fwd: need 1 <= nq <= S and out_seq >= nq");
@@ -1320,9 +1212,9 @@ extern "C" int clibd_attention_fwd(const void* qkv, int B, int S, int nheads, co
 #define LAUNCH_M(N, MSK, DRP)                                                                                     \
     do {                                                                                                          \
         /* The dropout forms of the persistent kernel that spill 2-10 registers at its 128-register cap (dropout with a key mask, dropout at sixteen tiles) were measured   */ \
-        /* against the spill-free per-head kernel in round 6 (knob = 0): 207 / 242 us persistent against 265-269 / 299 us per head at S = 220 / 250: the persistent forms stay */ \
+        /* against the spill-free per-head kernel in round 6: 207 / 242 us persistent against 265-269 / 299 us per head at S = 220 / 250: the persistent forms stay */ \
         /* Two masked forms would need 12-20 bytes of scratch at that cap and have no such measurement: they take the spill-free per-head kernel */ \
-        constexpr bool PERSIST_OK = (CLIBD_ATT_FWD_PERSISTENT_SPILLING || !(DRP && (MSK || N >= 16))) && !(MSK && ((N == 12 && DRP) || (N == 14 && !DRP))); \
+        constexpr bool PERSIST_OK = !(MSK && ((N == 12 && DRP) || (N == 14 && !DRP)));                           \
         bool persistent = false;                                                                                  \
         if constexpr (PERSIST_OK && N >= 12) {   /* S > 160: at S = 133 only 9 of the 16 waves have a tile and the per-head kernel wins; only these forms are instantiated */ \
             if (total >= 2 * num_cus) {                                                                           \
@@ -1361,8 +1253,7 @@ extern "C" int clibd_attention_fwd(const void* qkv, int B, int S, int nheads, co
 
 extern "C" int clibd_attention_bwd_sp(const void* qkv, const void* dout, const void* out, const void* o_lo, const float* lse, int B, int S,
                                       int nheads, void* dqkv, uint32_t drop_seed, int drop_thr16, float drop_scale, void* stream) {
-    if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "attention_bwd_sp: bad dropout threshold");
-    if (drop_thr16 > 0 && (unsigned long long)B * nheads * S * 256ull >= (1ull << 32)) return set_error(CLIBD_EINVAL, "attention_bwd_sp: dropout index overflow");
+    if (int e = check_dropout_args("attention_bwd_sp", B, S, nheads, drop_thr16)) return e;
     if (int e = att_check(qkv, B, S, nheads, "bwd_sp")) return e;
     if (!dout || !dqkv || !out || !o_lo || !lse) return set_error(CLIBD_EINVAL, "attention_bwd_sp: null pointer");
     if (S > 224) return set_error(CLIBD_EINVAL, "attention_bwd_sp: S must be <= 224 (five LDS images); use clibd_attention_bwd");
@@ -1395,8 +1286,7 @@ extern "C" int clibd_attention_bwd_sp(const void* qkv, const void* dout, const v
 extern "C" int clibd_attention_bwd(const void* qkv, const void* dout, int B, int S, int nheads, const int32_t* key_mask,
                                    void* dqkv, int nq, int dout_seq, uint32_t drop_seed, int drop_thr16, float drop_scale,
                                    void* stream) {
-    if (drop_thr16 < 0 || drop_thr16 > 65535) return set_error(CLIBD_EINVAL, "attention_bwd: bad dropout threshold");
-    if (drop_thr16 > 0 && (unsigned long long)B * nheads * S * 256ull >= (1ull << 32)) return set_error(CLIBD_EINVAL, "attention_bwd: dropout index overflow");
+    if (int e = check_dropout_args("attention_bwd", B, S, nheads, drop_thr16)) return e;
     if (int e = att_check(qkv, B, S, nheads, "bwd")) return e;
     if (!dout || !dqkv) return set_error(CLIBD_EINVAL, "attention_bwd: null pointer");
     if (nq < 1 || nq > S || dout_seq < nq) return set_error(CLIBD_EINVAL, "attention_bwd: need 1 <= nq <= S and dout_seq >= nq");
@@ -1424,8 +1314,8 @@ extern "C" int clibd_attention_bwd(const void* qkv, const void* dout, int B, int
     }
 #define LAUNCH_M(N, MSK, DRP)                                                                                     \
     do {                                                                                                          \
-        /* PAIR (two key tiles per wave in phase 2) for the long forms.  Sixteen tiles with dropout and no mask spill 10 registers at 256; the one-tile form (knob = 1) spills 4 and runs the same 384 us at S = 250: PAIR kept */ \
-        constexpr bool PR = (N >= 12) && !(CLIBD_ATT_BWD_S256_DROP_ONE_TILE && N == 16 && DRP && !MSK);             \
+        /* PAIR (two key tiles per wave in phase 2) for the long forms.  Sixteen tiles with dropout and no mask spill 10 registers at 256; the one-tile form spills 4 and runs the same 384 us at S = 250: PAIR kept */ \
+        constexpr bool PR = N >= 12;                                                                              \
         hipFuncSetAttribute((const void*)attention_bwd_kernel<N, PR, MSK, DRP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((attention_bwd_kernel<N, PR, MSK, DRP>), dim3(B * nheads), dim3(ATT_THREADS), lds, st,       \
                            (const unsigned short*)qkv, (const unsigned short*)dout, S, nheads, (const int*)key_mask, \

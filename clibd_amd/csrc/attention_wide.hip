@@ -1,101 +1,22 @@
 // Multi-head attention forward / backward for 128- and 192-wide heads (the newer BarcodeBERT towers: hidden 768 with 6 or 4 heads) on gfx950.
-// A self-contained unit beside attention.hip, which stays specialised for 64-wide heads: no key mask, no query prefix, no e4m3 output here.
+// Beside attention.hip, which stays specialised for 64-wide heads: no key mask, no query prefix, no e4m3 output here.  The LDS image (256- and
+// 384-byte rows, their swizzles and the bank-conflict argument), its staging, the fragment reads, the orientation and the row store are
+// attn_image.h's, shared with attention.hip and rollout.hip.
 //
 // One workgroup per (sequence, head): 4 waves, one per SIMD, in the backward and the short forward; 8 waves in the forward at S > 64.  Two [S_pad][DH] bf16 images of that head live in LDS: K and V in the forward and in
 // the backward's dQ phase, Q and dO in its dK / dV phase.  That is the rule behind the sequence limits: 2 x 256 x 256 B = 128 KiB at DH = 128,
 // 2 x 192 x 384 B = 144 KiB at DH = 192 (plus the row statistics), and 2 x 224 x 384 B would pass the 160 KiB of a compute unit.
 // The scores of one 16-query tile against ALL keys stay in registers (<= 16 key tiles x 4 fp32), so the softmax is an exact full-row softmax.
-//
-// Orientation, as in attention.hip ("key on the MFMA row, query on the lane"): S^T = K.Q^T via v_mfma_f32_16x16x32_bf16(A = K rows, B = Q rows)
-// leaves each lane ONE query (lane & 15) and keys 16 kt + 4 (lane >> 4) + reg.  Packed to bf16 those accumulators are the B operand of the product
-// that contracts over keys (P.V, dS.K) with the k-slot -> key map kappa(g, j) = 32 s + 16 (j >> 2) + 4 g + (j & 3); the other operand (V^T / K^T
-// rows = head dim) comes from ds_read_b64_tr_b16 with the same map.
-//
-// LDS images: rows of 256 B (DH = 128) or 384 B (DH = 192), filled by 16-byte LDS-DMA with the swizzle on the per-lane SOURCE address.  Chunk ch
-// (16 B) of row r sits at chunk ch ^ x(r):
-//   256-B rows: x = (r & 7) << 1.  A row starts on bank 0, so the 16-B slot of the 256-B bank row is ch ^ x.  The transposed read of a 32-lane half
-//     takes rows 8 n .. 8 n + 7 at one chunk pair: x >> 1 = r & 7 puts them on eight different 32-B slot pairs.  The ds_read_b128 row read works in
-//     16-lane groups of rows {0-3, 12-15} at chunk c and {4-11} at chunk c ^ 1 (or the reverse): even x, so the two sets take the even and the odd
-//     slots, and within a set r & 7 differs.  Both conflict-free.
-//   384-B rows: x = r & 6 (only the low three chunk bits move, so a chunk stays inside its aligned group of 8 of the 24).  Row r starts half a bank
-//     row further when r is odd: slot = (8 (r & 1) + (ch ^ x)) mod 16.  (r & 1, x) differs over 8 consecutive rows -> eight slot pairs for the
-//     transposed read; for the row read's two sets the parity of ch ^ x separates them and (r & 1, r & 6) differs within each.
-// Rows S .. S_pad-1 of every image are copies of row S-1 (finite bytes), key columns >= S get probability exactly 0, output rows >= S are never written.
-#include "common.h"
+// Key columns >= S get probability exactly 0, output rows >= S are never written.
+#include "attn_image.h"
 #include "../../include/clibd_hip.h"
 #include "../../include/clibd_hip_attn_wide.h"
-#include "host_util.h"
 #include <stdlib.h>
 
 namespace clibd {
 namespace wide {
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 constexpr int WAVES = 4;
-constexpr float NEG_BIG = -0x1p100f;   // a power of two (attention.hip): a padding score's exponent argument stays finite and its exp2 is exactly 0
-
-template <int DH>
-__device__ __forceinline__ int swz(int row) { return DH == 128 ? ((row & 7) << 1) : (row & 6); }
-template <int DH>
-__device__ __forceinline__ int img_off(int row, int ch) { return row * (2 * DH) + ((ch ^ swz<DH>(row)) << 4); }
-
-// rows [0, S_pad) x DH bf16 of one head (global row stride `ld` elements) into an LDS image; every LDS-DMA piece is 64 consecutive 16-B chunks
-template <int DH, int NW = WAVES>
-__device__ __forceinline__ void stage_image(char* img, const unsigned short* gbase, size_t ld, int S, int S_pad, int wave, int lane) {
-    constexpr int CH = DH / 8;
-    const int npieces = (S_pad * CH) >> 6;   // S_pad % 32 == 0: whole pieces
-    for (int p = wave; p < npieces; p += NW) {
-        const int L = p * 64 + lane;
-        const int row = L / CH, pos = L - row * CH;
-        glds16(gbase + (size_t)min(row, S - 1) * ld + ((pos ^ swz<DH>(row)) << 3), img + p * 1024);
-    }
-}
-
-template <int DH>
-__device__ __forceinline__ bf16x8 row_frag(const char* img, int row, int ks, int g) {
-    return *(const bf16x8*)(img + img_off<DH>(row, 4 * ks + g));
-}
-
-// transposed fragment: rows d = 16 dt + (lane & 15) of the image's transpose, k-slots (g, j) -> image rows kappa(g, j)
-template <int DH>
-__device__ __forceinline__ bf16x8 tr_frag(const char* img, int s, int dt, int lane) {
-    const int g = lane >> 4, i = lane & 15;
-    const int q = i >> 2, p = i & 3;
-    const int r0 = 32 * s + 4 * g + q;
-    const int ch = 2 * dt + (p >> 1);
-    const int a0 = img_off<DH>(r0, ch) + 8 * (p & 1);
-    const int a1 = img_off<DH>(r0 + 16, ch) + 8 * (p & 1);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + a1));
-    return (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-__device__ __forceinline__ bf16x8 pack_frag(const f32x4& a, const f32x4& b) {
-    bf16x8 r;
-    r[0] = (short)f2bf(a[0]); r[1] = (short)f2bf(a[1]); r[2] = (short)f2bf(a[2]); r[3] = (short)f2bf(a[3]);
-    r[4] = (short)f2bf(b[0]); r[5] = (short)f2bf(b[1]); r[6] = (short)f2bf(b[2]); r[7] = (short)f2bf(b[3]);
-    return r;
-}
-
-__device__ __forceinline__ void permlane16_swap_u32(unsigned& a, unsigned& b) {
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-}
-// One 16-row x DH-column output tile of a wave: lane (i = lane & 15, g = lane >> 4) holds v[dt][r] = element (row i, column 16 dt + 4 g + r).
-// A v_permlane16_swap between the lane rows g and g ^ 1 (a 2 x 2 transpose of the (dt, dt + 1) chunks) leaves every lane 16 contiguous bytes:
-// one dwordx4 store per tile pair.  Every lane must call this (the swap is a full-wave operation); `on` guards the stores only.
-template <int DT>
-__device__ __forceinline__ void store_rows(unsigned short* row, const f32x4 (&v)[DT], float mul, bool on, int g) {
-#pragma unroll
-    for (int pr = 0; pr < DT / 2; ++pr) {
-        unsigned a0 = pack2bf(v[2 * pr][0] * mul, v[2 * pr][1] * mul), a1 = pack2bf(v[2 * pr][2] * mul, v[2 * pr][3] * mul);
-        unsigned b0 = pack2bf(v[2 * pr + 1][0] * mul, v[2 * pr + 1][1] * mul), b1 = pack2bf(v[2 * pr + 1][2] * mul, v[2 * pr + 1][3] * mul);
-        permlane16_swap_u32(a0, b0);   // even g: columns 4g .. 4g+7 of tile 2 pr;  odd g: columns 4(g-1) .. 4(g-1)+7 of tile 2 pr + 1
-        permlane16_swap_u32(a1, b1);
-        if (on) *(uint4*)(row + 16 * (2 * pr + (g & 1)) + 8 * (g >> 1)) = make_uint4(a0, a1, b0, b1);
-    }
-}
 
 // scale factors of the four keys 16 kt + 4 g .. + 3 of query row `qrow` (= (b * nheads + h) * S + q)
 __device__ __forceinline__ void drop_quad(unsigned seed, unsigned qrow, int kt, int g, unsigned thr16, float scale, float (&f)[4]) {
@@ -125,8 +46,8 @@ __global__ __launch_bounds__(64 * NW) void attention_wide_fwd_kernel(const unsig
     const int nqt = (S + 15) >> 4;
     const float c2 = scale * 1.4426950408889634f;   // p = exp2(c2 s - c2 max): one FMA + one v_exp per score
     const bool last_live = S > 16 * (NKT - 1);      // NKT is even: the last key tile can be all padding (S = 133 -> 9 live tiles of 10)
-    stage_image<DH, NW>(k_img, qbase + H, ld, S, S_pad, wave, lane);
-    stage_image<DH, NW>(v_img, qbase + 2 * H, ld, S, S_pad, wave, lane);
+    img_stage<DH>(k_img, qbase + H, ld, S, S_pad, wave, lane, NW);
+    img_stage<DH>(v_img, qbase + 2 * H, ld, S, S_pad, wave, lane, NW);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -143,7 +64,7 @@ __global__ __launch_bounds__(64 * NW) void attention_wide_fwd_kernel(const unsig
             if (kt == NKT - 1 && !last_live) continue;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
-                sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(row_frag<DH>(k_img, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
+                sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(k_img, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
         }
         float mx = NEG_BIG;
 #pragma unroll
@@ -191,7 +112,7 @@ __global__ __launch_bounds__(64 * NW) void attention_wide_fwd_kernel(const unsig
             const bf16x8 pf = pack_frag(sc[2 * s], sc[2 * s + 1]);   // un-normalised probabilities (<= 1/(1-p)); 1/sum is applied to O
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt)
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag<DH>(v_img, s, dt, lane), pf, o[dt], 0, 0, 0);
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(v_img, s, dt, lane), pf, o[dt], 0, 0, 0);
         }
         store_rows<DT>(out + ((size_t)b * S + qc) * H + h * DH, o, inv, q < S, g);
     }
@@ -227,8 +148,8 @@ __global__ __launch_bounds__(64 * WAVES) void attention_wide_bwd_kernel(const un
     const int nt = (S + 15) >> 4;                     // live 16-row tiles, queries and keys alike
     const bool last_live = S > 16 * (NKT - 1);
 
-    stage_image<DH>(t0, qbase + H, ld, S, S_pad, wave, lane);
-    stage_image<DH>(t1, qbase + 2 * H, ld, S, S_pad, wave, lane);
+    img_stage<DH>(t0, qbase + H, ld, S, S_pad, wave, lane, WAVES);
+    img_stage<DH>(t1, qbase + 2 * H, ld, S, S_pad, wave, lane, WAVES);
     for (int r = threadIdx.x; r < S_pad; r += 64 * WAVES) {
         st_m[r] = r < S ? lse[(size_t)blockIdx.x * S + r] : -NEG_BIG;
         st_d[r] = 0.f;
@@ -255,8 +176,8 @@ __global__ __launch_bounds__(64 * WAVES) void attention_wide_bwd_kernel(const un
             if (kt == NKT - 1 && !last_live) continue;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(row_frag<DH>(t0, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
-                dp[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(row_frag<DH>(t1, kt * 16 + i, ks, g), dof[ks], dp[kt], 0, 0, 0);
+                sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(t0, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
+                dp[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(t1, kt * 16 + i, ks, g), dof[ks], dp[kt], 0, 0, 0);
             }
         }
         float dl = 0.f;
@@ -291,15 +212,15 @@ __global__ __launch_bounds__(64 * WAVES) void attention_wide_bwd_kernel(const un
             const bf16x8 dsf = pack_frag(d0, d1);   // dS / scale; the scale goes on the fp32 accumulators
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt)
-                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag<DH>(t0, s, dt, lane), dsf, dq[dt], 0, 0, 0);
+                dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(t0, s, dt, lane), dsf, dq[dt], 0, 0, 0);
         }
         store_rows<DT>(dqbase + (size_t)qc * ld, dq, scale, q < S, g);
     }
     __syncthreads();   // every wave is done reading the K / V images; delta is visible
 
     // ---------------- phase 2: per 16-key tile: dV, dK (query on the MFMA row, key on the lane) ----------------
-    stage_image<DH>(t0, qbase, ld, S, S_pad, wave, lane);
-    stage_image<DH>(t1, dobase, (size_t)H, S, S_pad, wave, lane);
+    img_stage<DH>(t0, qbase, ld, S, S_pad, wave, lane, WAVES);
+    img_stage<DH>(t1, dobase, (size_t)H, S, S_pad, wave, lane, WAVES);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -327,8 +248,8 @@ __global__ __launch_bounds__(64 * WAVES) void attention_wide_bwd_kernel(const un
                 f32x4 sv = (f32x4){0, 0, 0, 0}, dpv = (f32x4){0, 0, 0, 0};
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
-                    sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(row_frag<DH>(t0, qt * 16 + i, ks, g), kf[ks], sv, 0, 0, 0);
-                    dpv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(row_frag<DH>(t1, qt * 16 + i, ks, g), vf[ks], dpv, 0, 0, 0);
+                    sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(t0, qt * 16 + i, ks, g), kf[ks], sv, 0, 0, 0);
+                    dpv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<DH>(t1, qt * 16 + i, ks, g), vf[ks], dpv, 0, 0, 0);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -345,8 +266,8 @@ __global__ __launch_bounds__(64 * WAVES) void attention_wide_bwd_kernel(const un
             const bf16x8 dsf = pack_frag(dd[0], dd[1]);
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
-                dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag<DH>(t1, s, dt, lane), pf, dv[dt], 0, 0, 0);
-                dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag<DH>(t0, s, dt, lane), dsf, dk[dt], 0, 0, 0);
+                dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(t1, s, dt, lane), pf, dv[dt], 0, 0, 0);
+                dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_tr_frag<DH>(t0, s, dt, lane), dsf, dk[dt], 0, 0, 0);
             }
         }
         store_rows<DT>(dqbase + H + (size_t)kc * ld, dk, scale, key < S, g);
@@ -373,9 +294,7 @@ static int wide_check(const char* op, const void* qkv, int B, int S, int nheads,
     if (S > max_seq(head_dim)) return fail(op, head_dim == 128 ? "S must be <= 256 at head_dim 128" : "S must be <= 192 at head_dim 192 (LDS budget)");
     if ((long long)B * nheads > 0x7fffffffLL) return fail(op, "grid too large");
     if (!aligned16(qkv)) return fail(op, "alignment (16 bytes)");
-    if (drop_thr16 < 0 || drop_thr16 > 65535) return fail(op, "bad dropout threshold");
-    if (drop_thr16 > 0 && (unsigned long long)B * nheads * S * 256ull >= (1ull << 32)) return fail(op, "dropout index overflow");
-    return 0;
+    return check_dropout_args(op, B, S, nheads, drop_thr16);
 }
 
 }  // namespace wide

@@ -3,9 +3,9 @@
 //
 // Fused maps.  The attention kernels (attention.hip) are flash-style and never hold the probabilities P in memory, so there is nothing to
 // hook: P is recomputed here.  One workgroup (4 waves) owns 64 queries of one image — one 16-query tile per wave — and walks the heads.
-// Per head the K rows [S_pad][64] bf16 are staged into LDS in attention.hip's image layout (128-B rows, 16-B chunk index XOR (row & 7),
-// filled by 16-byte LDS-DMA), double buffered so that the next head's K arrives under this head's arithmetic.  S^T = K.Q^T runs on
-// v_mfma_f32_16x16x32_bf16 in attention.hip's orientation (key on the MFMA row, query on the lane): a lane holds ONE query (lane & 15)
+// Per head the K rows [S_pad][64] bf16 are staged into LDS as the attention kernels' head image (attn_image.h: layout, LDS-DMA staging,
+// row fragments, NEG_BIG), double buffered so that the next head's K arrives under this head's arithmetic.  S^T = K.Q^T runs on
+// v_mfma_f32_16x16x32_bf16 in the attention kernels' orientation (key on the MFMA row, query on the lane): a lane holds ONE query (lane & 15)
 // and the keys 16 kt + 4 (lane >> 4) + r, all of them in <= 64 accumulators, so the softmax is an exact full-row softmax in fp32.  The
 // probabilities fold into a second register set of the same shape (running sum, max or min) and after the last head one 16-byte store
 // per (lane, key tile) writes the fused row: S * ld floats per image reach memory, not heads * S * S.
@@ -18,10 +18,9 @@
 // Chain.  Only row 0 of the reference's matrix product is read, so the chain is a vector-matrix walk from the last selected layer to
 // the first: thread j accumulates sum_i v[i] a[i, j] as four interleaved fma chains over i, combined pairwise (loads coalesced across j).
 // One workgroup per image.
-#include "common.h"
+#include "attn_image.h"
 #include "../../include/clibd_hip.h"
 #include "../../include/clibd_hip_rollout.h"
-#include "host_util.h"
 
 namespace clibd {
 
@@ -30,25 +29,6 @@ constexpr int RO_WAVES = 4;
 constexpr int RO_DH = 64;
 constexpr int RO_MAX_S = 256;
 constexpr int SEL_THREADS = 1024;
-constexpr float RO_NEG_BIG = -0x1p100f;   // a masked score: exp2 of it underflows to exactly 0 (attention.hip's NEG_BIG)
-
-// attention.hip's LDS image of one head's rows: byte offset of 16-byte chunk `chunk` of row `row`
-__device__ __forceinline__ int ro_tile_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-
-// stage rows [0, S_pad) x 64 bf16 of one head (global row stride `ld` elements) into an LDS image; rows >= S repeat row S - 1 (their
-// scores are masked).  Every source row index is clamped to S - 1, every destination lies in [0, S_pad * 128).
-__device__ __forceinline__ void ro_stage_head_tile(char* lds_tile, const unsigned short* gbase, size_t ld, int S, int S_pad, int wave, int lane) {
-    const int prow = lane >> 3;
-    const int chunk = (lane & 7) ^ prow;
-    for (int p = wave; p < (S_pad >> 3); p += RO_WAVES) {
-        const int row = min(p * 8 + prow, S - 1);
-        glds16(gbase + (size_t)row * ld + chunk * 8, lds_tile + p * 1024);
-    }
-}
-
-__device__ __forceinline__ bf16x8 ro_lds_row_frag(const char* tile, int row, int ks, int g) {
-    return *(const bf16x8*)(tile + ro_tile_off(row, 4 * ks + g));
-}
 
 // NKT: 16-key tiles held per lane (S <= 16 NKT).  Grid: B * ngroups workgroups, workgroup (b, grp) owns query tiles 4 grp .. 4 grp + 3.
 template <int NKT>
@@ -77,7 +57,7 @@ __global__ __launch_bounds__(RO_THREADS) void attn_fused_maps_kernel(const unsig
     bf16x8 qn[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) qn[ks] = *(const bf16x8*)(base + (size_t)qc * ldq + 32 * ks + 8 * g);
-    ro_stage_head_tile(smem, base + H, ldq, S, S_pad, wave, lane);
+    img_stage<RO_DH>(smem, base + H, ldq, S, S_pad, wave, lane, RO_WAVES);
 
     for (int h = 0; h < nheads; ++h) {
         // head h's K image and Q fragment have arrived; every wave is done with the other image (it read it for head h - 1)
@@ -87,24 +67,24 @@ __global__ __launch_bounds__(RO_THREADS) void attn_fused_maps_kernel(const unsig
         if (h + 1 < nheads) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) qn[ks] = *(const bf16x8*)(base + (size_t)qc * ldq + (h + 1) * RO_DH + 32 * ks + 8 * g);
-            ro_stage_head_tile(smem + ((h + 1) & 1) * IMG, base + H + (h + 1) * RO_DH, ldq, S, S_pad, wave, lane);
+            img_stage<RO_DH>(smem + ((h + 1) & 1) * IMG, base + H + (h + 1) * RO_DH, ldq, S, S_pad, wave, lane, RO_WAVES);
         }
         if (!active) continue;
         const char* kt_lds = smem + (h & 1) * IMG;
         int nlive = S - 4 * g;   // this lane's key 16 kt + 4 g + r is live iff 16 kt + r < nlive
         asm volatile("" : "+v"(nlive));   // re-derived per head: hoisted out of the head loop, the 64 compare masks cost the scalar registers
         f32x4 sc[NKT];
-        float mx = RO_NEG_BIG;
+        float mx = NEG_BIG;
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
             sc[kt] = (f32x4){0, 0, 0, 0};
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ro_lds_row_frag(kt_lds, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
+                sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(img_row_frag<RO_DH>(kt_lds, kt * 16 + i, ks, g), qf[ks], sc[kt], 0, 0, 0);
             if (kt * 16 + 15 >= S) {   // a tile that holds padded keys
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (kt * 16 + r >= nlive) sc[kt][r] = RO_NEG_BIG;
+                    if (kt * 16 + r >= nlive) sc[kt][r] = NEG_BIG;
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[kt][r]);
