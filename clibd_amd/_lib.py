@@ -195,6 +195,14 @@ ATTN_WIDE_SIGNATURES = {
     "clibd_attention_wide_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, C.c_uint32, c_int, c_float, c_void_p]),
 }
 
+# masked-k-mer pre-training (include/clibd_hip_mlm.h): a tenth additive table, bound after the other nine
+MLM_SIGNATURES = {
+    "clibd_mlm_mask": (c_int, [c_void_p, c_int, c_int, C.c_uint32, c_int, C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "clibd_rows_gather_bf16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "clibd_rows_scatter_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "clibd_mlm_ce_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7  # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -220,7 +228,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items())
                               + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(INSECT_SIGNATURES.items()) + list(MLP_SIGNATURES.items())
-                              + list(ATTN_WIDE_SIGNATURES.items())):
+                              + list(ATTN_WIDE_SIGNATURES.items()) + list(MLM_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1,0 +1,310 @@
+"""Masked-k-mer pre-training of the BarcodeBERT DNA tower on the MI355X HIP engine: the link between a collection of barcodes and the
+checkpoint `load_pre_trained_bioscan_bert` reads (`bioscan_bert_checkpoint`), as `clibd_amd.simclr` is for the image tower.
+
+The objective is HF `BertForMaskedLM(input_ids, labels)` — what the reference instantiates (model/dna_encoder.py:35-37) — with labels =
+-100 outside the masked positions: mean cross-entropy over the masked k-mers.  The tower is `clibd_amd.towers.BertTower` under full
+fine-tuning with head="hidden" (post-LN stack, embedding gradients, train-mode dropout, deterministic mode: all the DNA tower's); the
+vocabulary head runs on the MASKED rows only: gather -> transform dense + GELU -> LayerNorm -> decoder GEMM to bf16 logits -> the fused
+cross-entropy of csrc/mlm.hip, which leaves the gradient in the logits' place; the backward is the mirror and ends in a scatter into the
+[B*S, H] gradient of the top hidden state.  bf16 GEMM operands, fp32 accumulation, statistics, loss and master weights.
+
+The sampler (csrc/mlm.hip, `mask_tokens`): per sequence n_mask = max(1, int(mask_ratio * (S - 1))) positions; position 0 — the 0
+`get_sequence_pipeline` prepends — is never chosen; position s >= 1 of sequence b gets the key (id == unk_id, lowbias32((b*S + s) ^
+seed), s) and the n_mask smallest keys are chosen, so padding k-mers are taken only when real ones run out; a chosen id becomes mask_id,
+its target the original id, or -100 where that was unk_id.  BarcodeBERT's own training code is not part of the reference, so this rule is
+this project's and is pinned by the restatement in tests/mlm_reference.py.
+
+One stated divergence from a default-configured HF model: BertConfig's default pad_token_id = 0 is this vocabulary's <MASK>, which makes
+row 0 of HF's word table an nn.Embedding padding row whose lookup gradient torch drops.  The embedding backward here has no padding row
+(it never had one): the mask token's embedding trains through the lookup like every other row, as an HF model built with
+pad_token_id=None does (the golden's models are built so).
+
+Out of scope (each raises or simply does not exist here):
+  - HF-style `labels [B, S]` with a free number of masked positions per sequence: every sequence has exactly n_mask rows;
+  - 80/10/10 replacement (a chosen position always becomes mask_id), whole-word or span masking;
+  - the remote-code tokenizer of the newer BarcodeBERT checkpoints (strings go through the k-mer kernel, `eval.tokenize_barcodes`);
+  - data-parallel pre-training (the flat gradient bucket is one all-reduce message, but nothing here issues it and it is unmeasured);
+  - fp8 modes for this step;
+  - S > 256 (S > 192 with 192-wide heads), and an attention mask with wide heads: full sequences only, as the towers.
+The upstream gradient of the loss is taken as a device scalar; the loss's own gradient is written by the forward's cross-entropy kernel.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from .engine import BF16, F32, GradBucket, NotSupportedYet, _f32c, _ordered, linear_wgrad, ln_param_grads
+from .towers import BertTower
+
+CONFIG_KEYS = ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "max_position_embeddings",
+               "layer_norm_eps", "hidden_dropout_prob", "attention_probs_dropout_prob")
+
+
+def n_mask_for(S: int, mask_ratio: float) -> int:
+    if not 0.0 < mask_ratio <= 1.0:
+        raise ValueError("mask_ratio must be in (0, 1]")
+    return max(1, int(mask_ratio * (S - 1)))
+
+
+def mask_tokens(ids: torch.Tensor, mask_ratio: float = 0.5, seed: Optional[int] = None, mask_id: int = 0, unk_id: int = 2):
+    """ids int64 [B, S] on the device -> (masked_ids [B, S], rows int32 [B * n_mask], targets int64 [B * n_mask], n_valid int32 [1]), all
+    on the device (the module docstring has the rule).  seed=None draws it from the CPU generator, as the towers draw their dropout
+    base: reproducible under torch.manual_seed, and no device synchronisation."""
+    if ids.dim() != 2:
+        raise ValueError("mask_tokens: ids must be [B, S]")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+    return ops.mlm_mask(ids.to(torch.int64).contiguous(), seed, n_mask_for(ids.shape[1], mask_ratio), mask_id, unk_id)
+
+
+class _MLMFn(torch.autograd.Function):
+    """forward(owner, masked_ids, rows, targets, n_valid, *trainable parameters) -> (loss, correct)"""
+
+    @staticmethod
+    def forward(ctx, owner, masked_ids, rows, targets, n_valid, *params):
+        loss, correct, state = owner._forward(masked_ids, rows, targets, n_valid, True)
+        ctx.owner, ctx.state, ctx.nparams = owner, state, len(params)
+        ctx.mark_non_differentiable(correct)
+        return loss, correct
+
+    @staticmethod
+    def backward(ctx, dloss, _dcorrect):
+        owner, state = ctx.owner, ctx.state
+        if state is None:
+            raise RuntimeError("backward twice through one pre-training forward")
+        ctx.state = None
+        params = owner.trainable_params()
+        assert len(params) == ctx.nparams
+        sink = owner.grad_sink
+        if sink is not None and all(id(p) in sink for p in params):
+            owner._backward(dloss, state, sink)   # the optimizer's flat bucket (clibd_amd.optim.FusedAdamW): accumulate straight into it
+            return (None,) * (5 + len(params))
+        bucket = GradBucket(params)
+        owner._backward(dloss, state, bucket.views)
+        return (None, None, None, None, None, *bucket.ordered())
+
+
+class BarcodeBERTForPreTraining(nn.Module):
+    """`model`: a BertForMaskedLM — the parameter container of clibd_amd.model or transformers' class; only parameters are read.  Every
+    parameter is trainable (no LoRA).  `state_dict()` has exactly the HF keys (`bert. ...`, `cls.predictions. ...`).
+    tie_word_embeddings: None reads `model.config.tie_word_embeddings` (absent: True, HF's default).  Tied: `cls.predictions.decoder.weight`
+    IS the word-embedding Parameter and `decoder.bias` IS `cls.predictions.bias`, as in HF; both names stay in the state dict.  Untied:
+    four separate parameters (`cls.predictions.bias` then takes no part, as in HF)."""
+
+    def __init__(self, model, tie_word_embeddings: Optional[bool] = None):
+        super().__init__()
+        self.bert, self.cls, self.config = model.bert, model.cls, getattr(model, "config", None)
+        if tie_word_embeddings is None:
+            tie_word_embeddings = bool(getattr(self.config, "tie_word_embeddings", True))
+        self.tie_word_embeddings = bool(tie_word_embeddings)
+        pred = self.cls.predictions
+        word = self.bert.embeddings.word_embeddings.weight
+        if tuple(pred.decoder.weight.shape) != tuple(word.shape):
+            raise ValueError("BarcodeBERTForPreTraining: the decoder must span the vocabulary (a replaced decoder is a fine-tuned tower)")
+        if self.tie_word_embeddings:
+            pred.decoder.weight = word
+            pred.decoder.bias = pred.bias
+        elif pred.decoder.weight is word or pred.decoder.bias is pred.bias:
+            raise ValueError("BarcodeBERTForPreTraining: the model is tied; untie it before asking for tie_word_embeddings=False")
+        if any(hasattr(l.attention.self.query, "w_a") for l in self.bert.encoder.layer):
+            raise NotSupportedYet("BarcodeBERTForPreTraining: LoRA adapters (pre-training is a full fine-tune)")
+        V, H = word.shape
+        if V > 8192 or H % 64:
+            raise NotSupportedYet(f"BarcodeBERTForPreTraining: vocabulary {V} > 8192 (k <= 6) or a hidden size {H} that is no multiple of 64")
+        for p in self.parameters():
+            p.requires_grad_(True)
+        self.grad_sink = None   # {id(param): fp32 accumulation tensor}: see attach()
+        self._tower = None
+
+    def tower(self) -> BertTower:
+        if self._tower is None:
+            self._tower = BertTower(self.bert, "hidden", {})
+        return self._tower
+
+    def set_deterministic(self, enabled: bool = True):
+        """fixed-order reductions in the whole backward (clibd_amd.engine.default_deterministic): the same weights, batch, mask and dropout
+        seeds give the same loss, gradients and update bit for bit.  Under tying the decoder's weight gradient goes into the shared
+        buffer first, the embedding-lookup gradient second, in every mode."""
+        self.tower().deterministic = bool(enabled)
+        return self
+
+    def attach(self, optimizer):
+        """wire a clibd_amd.optim.FusedAdamW built over `self.parameters()`: the backward accumulates into its flat gradient bucket"""
+        if not hasattr(optimizer, "flat_g"):
+            raise NotSupportedYet("BarcodeBERTForPreTraining.attach: needs clibd_amd.optim.FusedAdamW (the flat gradient bucket)")
+        self.grad_sink = {id(p): p.grad for p in optimizer.param_groups[0]["params"]}
+        return self
+
+    def _head(self):
+        pred = self.cls.predictions
+        return pred.transform.dense, pred.transform.LayerNorm, pred.decoder
+
+    def trainable_params(self):
+        """the tower's parameters, then the head's; a tied parameter once"""
+        td, tln, dec = self._head()
+        ps, seen = [], set()
+        for p in self.tower().trainable_params() + [td.weight, td.bias, tln.weight, tln.bias, dec.weight, dec.bias]:
+            if p.requires_grad and id(p) not in seen:
+                seen.add(id(p))
+                ps.append(p)
+        return ps
+
+    def forward(self, masked_ids, rows, targets, n_valid):
+        """(loss fp32 scalar, correct int32 [1]) on the device; under autograd `loss.backward()` produces every parameter gradient."""
+        params = self.trainable_params()
+        if torch.is_grad_enabled() and params:
+            return _MLMFn.apply(self, masked_ids, rows, targets, n_valid, *params)
+        with torch.no_grad():
+            loss, correct, _ = self._forward(masked_ids, rows, targets, n_valid, False)
+        return loss, correct
+
+    def _forward(self, masked_ids, rows, targets, n_valid, save):
+        tw = self.tower()
+        tw.training = self.training
+        if tw.stack.fp8 is not None:
+            raise NotSupportedYet("BarcodeBERTForPreTraining: the fp8 forward")
+        x_top, state = tw._forward((masked_ids, None, None), save)   # [M, H] bf16
+        loss, correct, head = self._head_forward(x_top, rows, targets, n_valid)
+        if save:
+            state.update(mlm=head)
+        return loss, correct, state
+
+    def _head_forward(self, x_top, rows, targets, n_valid):
+        """the vocabulary head on the rows `rows` of x_top bf16 [M, H]: (loss, correct, what the backward needs)"""
+        td, tln, dec = self._head()
+        M, H = x_top.shape
+        dev = x_top.device
+        rows = rows.to(torch.int32).contiguous()
+        R = rows.numel()
+        xg = ops.rows_gather(x_top, rows)
+        wt = ops.cast_bf16(_f32c(td.weight))
+        hpre = torch.empty((R, H), dtype=BF16, device=dev)
+        g = torch.empty((R, H), dtype=F32, device=dev)
+        ops.gemm_nt(xg, wt, bias=_f32c(td.bias), act=ops.ACT_GELU, out_pre=hpre, out_f32=g)
+        hln = torch.empty((R, H), dtype=BF16, device=dev)
+        st = torch.empty((R, 2), dtype=F32, device=dev)
+        ops.layernorm_fwd(g, _f32c(tln.weight), _f32c(tln.bias), float(tln.eps), y_bf16=hln, stats=st)
+        # the decoder over a vocabulary that is no multiple of the GEMM's tiles (4^k + 3): zero rows pad the weight image to a multiple of
+        # 64 — the N granule of the forward and the K granule of the dgrad — and the cross-entropy never reads the padding columns
+        V = dec.weight.shape[0]
+        Vp = (V + 63) // 64 * 64
+        wp, bp = torch.zeros((Vp, H), dtype=BF16, device=dev), torch.zeros((Vp,), dtype=F32, device=dev)
+        wp[:V].copy_(ops.cast_bf16(_f32c(dec.weight)))
+        bp[:V].copy_(_f32c(dec.bias))
+        logits = torch.empty((R, Vp), dtype=BF16, device=dev)
+        ops.gemm_nt(hln, wp, bias=bp, out_bf16=logits)
+        loss, correct, _ = ops.mlm_ce_(logits, V, targets.to(torch.int64).contiguous(), n_valid)   # logits now holds d loss / d logits
+        return loss.reshape(()), correct, dict(rows=rows, xg=xg, hpre=hpre, g=g, st=st, hln=hln, dlogits=logits, wp=wp, M=M, V=V)
+
+    def _backward(self, dloss, state, grads):
+        dx = self._head_backward(dloss, state.pop("mlm"), grads)
+        self.tower()._backward(dx, state, grads)
+
+    def _head_backward(self, dloss, s, grads):
+        """the head's parameter gradients into `grads` (accumulating); returns the gradient of the top hidden state, bf16 [M, H]"""
+        td, tln, dec = self._head()
+        det = self.tower().deterministic
+        dl, hln, V, M = s["dlogits"], s["hln"], s["V"], s["M"]
+        R, H = hln.shape
+        dev = dl.device
+        dl.mul_(dloss.detach().reshape(()).to(BF16))   # the upstream gradient (loss.backward(): exactly 1)
+        # decoder: dW [V, H] += dlogits^T hln (under tying into the word table's buffer, ahead of the lookup gradient), db += column sums
+        csum = torch.zeros((dl.shape[1],), dtype=F32, device=dev)
+        dyT = ops.transpose_bf16(dl, pad_to=128, colsum=csum if id(dec.bias) in grads else None)   # [Vp, Rp] (+ fixed-order column sums)
+        if id(dec.bias) in grads:
+            grads[id(dec.bias)].view(-1).add_(csum[:V])
+        if id(dec.weight) in grads:
+            xT = ops.transpose_bf16(hln, pad_to=128)   # [H, Rp]
+            Rp = dyT.shape[1]
+            gw = grads[id(dec.weight)].view(V, H)
+            split = 1 if det else max(1, min(32, Rp // 2048))
+            if Rp >= 4096 and ops.gemm_nt_splitk(dyT[:V], xT, gw, accumulate=True):
+                pass   # long contraction: the 256x256 split-K workspace path, partials summed in a fixed order
+            elif split > 1:
+                ops.gemm_nt(dyT[:V], xT, out_f32=gw, split_k=split)
+            else:
+                ops.gemm_nt(dyT[:V], xT, out_f32=gw, residual=gw)
+        dhln = torch.empty((R, H), dtype=BF16, device=dev)
+        ops.gemm_nt(dl, ops.transpose_bf16(s["wp"], pad_to=64), out_bf16=dhln)   # [R, Vp] x ([H, Vp])^T: the padding contracts zeros
+        dg = torch.empty((R, H), dtype=BF16, device=dev)
+        ops.layernorm_bwd(dhln, s["g"], s["st"], _f32c(tln.weight), dx_bf16=dg, **ln_param_grads(grads, tln.weight, tln.bias, det))
+        dhpre = ops.gelu_bwd(dg, s["hpre"])
+        linear_wgrad(dhpre, s["xg"], [td.weight], [td.bias], grads, **_ordered(det))
+        dxg = torch.empty((R, H), dtype=BF16, device=dev)
+        ops.gemm_nt(dhpre, ops.cast_transpose_bf16(_f32c(td.weight)), out_bf16=dxg)
+        return ops.rows_scatter(dxg, s["rows"], M)   # zeros in the rows that were not masked
+
+
+def _ids_of(batch, device, k: int) -> torch.Tensor:
+    if isinstance(batch, torch.Tensor):
+        return batch.to(device=device, dtype=torch.int64)
+    if isinstance(batch, (list, tuple)) and batch and all(isinstance(s, str) for s in batch):
+        from .eval import tokenize_barcodes
+
+        return tokenize_barcodes(list(batch), device, k=k)
+    raise TypeError("pre-training batches are int64 [b, S] token ids or lists of barcode strings")
+
+
+def _kmer_k(model) -> int:
+    V = model.bert.embeddings.word_embeddings.weight.shape[0]
+    for k in range(1, 7):
+        if 4 ** k + 3 == V:
+            return k
+    raise NotSupportedYet(f"a vocabulary of {V} entries is not <MASK>, <CLS>, <UNK> + 4^k k-mers: pass token ids")
+
+
+def pretrain_step(model: BarcodeBERTForPreTraining, batch, optimizer, mask_ratio: float = 0.5, seed: Optional[int] = None):
+    """mask -> forward -> backward -> optimizer step on one batch (token ids or barcode strings); returns the device tensors
+    (loss, correct, n_valid).  No host synchronisation."""
+    dev = next(model.parameters()).device
+    ids = _ids_of(batch, dev, _kmer_k(model) if not isinstance(batch, torch.Tensor) else 0)
+    masked, rows, targets, n_valid = mask_tokens(ids, mask_ratio, seed)
+    optimizer.zero_grad()
+    loss, correct = model(masked, rows, targets, n_valid)
+    loss.backward()
+    optimizer.step()
+    return loss.detach(), correct, n_valid
+
+
+def pretrain_epoch(model: BarcodeBERTForPreTraining, loader, optimizer, scheduler=None, mask_ratio: float = 0.5, log_every: int = 0):
+    """One pass over `loader` (int64 [b, S] ids or lists of barcode strings) in train mode.  `optimizer`: clibd_amd.optim.FusedAdamW over
+    model.parameters(), wired to the backward here as simclr.py wires its own; `scheduler` (optional) is stepped per batch.  The loss and
+    the masked-token hits accumulate on the device and are fetched once, at the end (log_every > 0 fetches the running mean every that many
+    steps, a host synchronisation each).  Returns {"loss": mean step loss, "accuracy": hits / valid targets, "steps": n}."""
+    if hasattr(optimizer, "flat_g"):
+        model.attach(optimizer)
+    model.train()
+    dev = next(model.parameters()).device
+    acc = torch.zeros((3,), dtype=torch.float64, device=dev)   # sum of step losses, hits, valid targets
+    n = 0
+    for batch in loader:
+        loss, correct, n_valid = pretrain_step(model, batch, optimizer, mask_ratio)
+        acc += torch.stack([loss.double(), correct[0].double(), n_valid[0].double()])
+        n += 1
+        if scheduler is not None:
+            scheduler.step()
+        if log_every and n % log_every == 0:
+            s = acc.tolist()
+            print(f"step {n}\tloss {s[0] / n:.4f}\tmasked-token accuracy {s[1] / max(s[2], 1.0):.4f}")
+    s = acc.tolist()   # the one host fetch of the epoch
+    return {"loss": s[0] / max(n, 1), "accuracy": s[1] / max(s[2], 1.0), "steps": n}
+
+
+def bert_config_of(model) -> dict:
+    cfg = getattr(model, "config", None)
+    if cfg is None:
+        raise ValueError("save_pretrained: the model carries no config")
+    out = {k: getattr(cfg, k) for k in CONFIG_KEYS}
+    out["tie_word_embeddings"] = bool(getattr(model, "tie_word_embeddings", getattr(cfg, "tie_word_embeddings", True)))
+    return out
+
+
+def save_pretrained(model: BarcodeBERTForPreTraining, path) -> dict:
+    """{"model": state dict with the HF keys (CPU tensors), "bert_config": {...}}: the file `load_pre_trained_bioscan_bert(path)` and
+    `load_clip_model` (`bioscan_bert_checkpoint`) read unchanged.  Under tying the shared tensors are written under both names."""
+    ckpt = {"model": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, "bert_config": bert_config_of(model)}
+    torch.save(ckpt, path)
+    return ckpt

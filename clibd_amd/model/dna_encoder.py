@@ -23,7 +23,8 @@ from .image_encoder import _ParamOnly
 class BertConfigLite:
     def __init__(self, vocab_size=30522, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
                  max_position_embeddings=512, type_vocab_size=2, layer_norm_eps=1e-12, hidden_dropout_prob=0.1,
-                 attention_probs_dropout_prob=0.1, **unused):
+                 attention_probs_dropout_prob=0.1, tie_word_embeddings=True, **unused):
+        self.tie_word_embeddings = bool(tie_word_embeddings)   # HF's default; read by clibd_amd.mlm only (the containers below never tie)
         self.vocab_size, self.hidden_size, self.num_hidden_layers = vocab_size, hidden_size, num_hidden_layers
         self.num_attention_heads, self.intermediate_size = num_attention_heads, intermediate_size
         self.max_position_embeddings, self.type_vocab_size, self.layer_norm_eps = max_position_embeddings, type_vocab_size, layer_norm_eps

@@ -1629,3 +1629,76 @@ def logits_topk(logits: torch.Tensor, k: int = 5):
     idx = torch.empty((B, k), dtype=I64, device=logits.device)
     check(_lib.load().clibd_logits_topk(logits.data_ptr(), max(ld, Ccls), B, Ccls, k, val.data_ptr(), idx.data_ptr(), _stream()), "logits_topk")
     return val, idx
+
+
+# ---- masked-k-mer pre-training (include/clibd_hip_mlm.h) ---------------------------------------------------------------------------------
+MLM_IGNORE = -100   # CLIBD_MLM_IGNORE: torch's ignore_index
+
+
+def mlm_mask(ids: torch.Tensor, seed: int, n_mask: int, mask_id: int = 0, unk_id: int = 2):
+    """The position sampler (clibd_mlm_mask): ids int64 [B, S] -> (masked int64 [B, S], rows int32 [B * n_mask], targets int64 [B * n_mask],
+    n_valid int32 [1]).  n_mask positions per sequence, never position 0, padding k-mers (unk_id) last; rows = b * S + s ascending;
+    a target is the original id, or MLM_IGNORE where that was unk_id.  Nothing is read back."""
+    _chk(ids, I64, "ids")
+    if ids.dim() != 2:
+        raise ValueError("mlm_mask: ids must be [B, S]")
+    B, S = ids.shape
+    n_mask = int(n_mask)
+    if B < 1 or not 2 <= S <= 256 or not 1 <= n_mask <= S - 1:
+        raise ValueError("mlm_mask: need B >= 1, 2 <= S <= 256 and 1 <= n_mask <= S - 1")
+    dev = ids.device
+    masked = torch.empty_like(ids)
+    rows = torch.empty((B * n_mask,), dtype=I32, device=dev)
+    targets = torch.empty((B * n_mask,), dtype=I64, device=dev)
+    n_valid = torch.empty((1,), dtype=I32, device=dev)
+    check(_lib.load().clibd_mlm_mask(ids.data_ptr(), B, S, int(seed) & 0xFFFFFFFF, n_mask, int(mask_id), int(unk_id), masked.data_ptr(), rows.data_ptr(),
+                                     targets.data_ptr(), n_valid.data_ptr(), _stream()), "mlm_mask")
+    return masked, rows, targets, n_valid
+
+
+def rows_gather(x: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """x bf16 [M, H] (H % 8 == 0), rows int32 [R] -> x[rows] bf16 [R, H] (clibd_rows_gather_bf16)."""
+    _chk(x, BF16, "x"); _chk(rows, I32, "rows")
+    if x.dim() != 2 or rows.dim() != 1 or rows.numel() < 1 or x.shape[1] % 8:
+        raise ValueError("rows_gather: x must be [M, H] with H % 8 == 0 and rows a non-empty vector")
+    M, H = x.shape
+    out = torch.empty((rows.numel(), H), dtype=BF16, device=x.device)
+    check(_lib.load().clibd_rows_gather_bf16(x.data_ptr(), M, H, rows.data_ptr(), rows.numel(), out.data_ptr(), _stream()), "rows_gather_bf16")
+    return out
+
+
+def rows_scatter(src: torch.Tensor, rows: torch.Tensor, M: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The transpose of rows_gather (clibd_rows_scatter_bf16): bf16 [M, H] with out[rows[i]] = src[i] and zeros in every other row; the
+    call writes all of `out` (a fresh tensor unless one is passed).  The rows must be distinct: a repeated index is not detected."""
+    _chk(src, BF16, "src"); _chk(rows, I32, "rows")
+    if src.dim() != 2 or tuple(rows.shape) != (src.shape[0],) or src.shape[0] < 1 or src.shape[1] % 8:
+        raise ValueError("rows_scatter: src must be [R, H] with H % 8 == 0 and rows [R]")
+    R, H = src.shape
+    if out is None:
+        out = torch.empty((int(M), H), dtype=BF16, device=src.device)
+    else:
+        _chk(out, BF16, "out")
+        if tuple(out.shape) != (int(M), H):
+            raise ValueError(f"rows_scatter: out must be [{int(M)}, {H}]")
+    check(_lib.load().clibd_rows_scatter_bf16(src.data_ptr(), rows.data_ptr(), R, int(M), H, out.data_ptr(), _stream()), "rows_scatter_bf16")
+    return out
+
+
+def mlm_ce_(logits: torch.Tensor, V: int, targets: torch.Tensor, n_valid: torch.Tensor):
+    """Cross-entropy over the first V columns of bf16 logits [R, ld] (unit inner stride, ld % 8 == 0), IN PLACE (clibd_mlm_ce_bf16): returns
+    (loss fp32 [1], correct int32 [1], row_loss fp32 [R]) and leaves d loss / d logits in `logits` — (softmax - onehot) / max(n_valid, 1),
+    exactly 0 in rows whose target is MLM_IGNORE and in the columns from V on.  A target outside {MLM_IGNORE} U [0, V) sets bit 0 of
+    `ce_error_word` and counts as ignored."""
+    _chk(logits, BF16, "logits", contiguous=False); _chk(targets, I64, "targets"); _chk(n_valid, I32, "n_valid")
+    ld = _rowmajor(logits, "logits")
+    R = logits.shape[0]
+    V = int(V)
+    if R < 1 or not 1 <= V <= min(8192, logits.shape[1]) or tuple(targets.shape) != (R,) or n_valid.numel() != 1:
+        raise ValueError("mlm_ce_: need R >= 1, 1 <= V <= min(8192, columns), targets [R] and a one-element n_valid")
+    dev = logits.device
+    row_loss = torch.empty((R,), dtype=F32, device=dev)
+    loss = torch.empty((1,), dtype=F32, device=dev)
+    correct = torch.empty((1,), dtype=I32, device=dev)
+    check(_lib.load().clibd_mlm_ce_bf16(logits.data_ptr(), ld, targets.data_ptr(), R, V, n_valid.data_ptr(), row_loss.data_ptr(), loss.data_ptr(),
+                                        correct.data_ptr(), ce_error_word(dev).data_ptr(), _stream()), "mlm_ce_bf16")
+    return loss, correct, row_loss

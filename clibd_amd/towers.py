@@ -2,9 +2,11 @@
 
 ViTTower      = timm vit_base_patch16_224 forward/backward + LoRA(q,v) + trainable head
                 (reference: model/image_encoder.py:49-107; timm created at model/simple_clip.py:150-153)
-BertTower     = HF BERT encoder (post-LN) + LoRA(query,value) with one of two heads:
+BertTower     = HF BERT encoder (post-LN) + LoRA(query,value) with one of three heads:
    head="mlm"   BertForMaskedLM transform + replaced decoder, softmax(-1).mean(1)   (model/dna_encoder.py:80-137)
    head="mean"  last_hidden_state.mean(1) -> proj                                  (model/language_encoder.py:36-89)
+   head="hidden" no head: the top hidden state [B*S, H] bf16 goes out and its gradient comes in (clibd_amd.mlm puts the masked-LM
+                head on the gathered rows)
 MLPTower      = Linear, ReLU, Linear, ReLU, Linear over pre-extracted feature rows, fp32-grade, no transformer stack
                 (reference: model/mlp.py:23-37; built at model/simple_clip.py:172-175, 211-214 for `input_type: feature`)
 """
@@ -239,7 +241,9 @@ class BertTower(_Tower):
         """bert: HF-shaped BertModel tree (embeddings.{word,position,token_type}_embeddings, embeddings.LayerNorm,
         encoder.layer[i].attention.self.{query,key,value}, attention.output.{dense,LayerNorm}, intermediate.dense,
         output.{dense,LayerNorm}); query/value may be LoRA wrappers exposing .w/.w_a/.w_b.
-        head="mlm": head_modules = {transform_dense, transform_ln, decoder};  head="mean": {proj}."""
+        head="mlm": head_modules = {transform_dense, transform_ln, decoder};  head="mean": {proj};  head="hidden": {}."""
+        if head not in ("mlm", "mean", "hidden"):
+            raise ValueError(f"BertTower: unknown head {head!r}")
         self.bert, self.head_kind, self.hm = bert, head, head_modules
         emb = bert.embeddings
         H = emb.word_embeddings.weight.shape[1]
@@ -271,7 +275,7 @@ class BertTower(_Tower):
                 ps += L.lora.tensors()
         if self.head_kind == "mlm":
             ps += [self.hm["decoder"].weight, self.hm["decoder"].bias]
-        else:
+        elif self.head_kind == "mean":
             ps += [self.hm["proj"].weight, self.hm["proj"].bias]
         return ps + self.stack.base_params() + self._frozen_extra()
 
@@ -292,8 +296,10 @@ class BertTower(_Tower):
         if self.head_kind == "mlm":
             head = [self.hm["decoder"].weight, self.hm["decoder"].bias, self.hm["transform_dense"].weight, self.hm["transform_dense"].bias,
                     self.hm["transform_ln"].weight, self.hm["transform_ln"].bias]
-        else:
+        elif self.head_kind == "mean":
             head = [self.hm["proj"].weight, self.hm["proj"].bias]
+        else:
+            head = []
         return self._stack_groups(head, [emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight,
                                          emb.LayerNorm.weight, emb.LayerNorm.bias])
 
@@ -368,6 +374,8 @@ class BertTower(_Tower):
             out = ops.softmax_mean_fwd(logits, B, S)
             if save:
                 state.update(hpre=hpre, g=g, st=st, hln=hln, logits=logits)
+        elif self.head_kind == "hidden":
+            out = x_bf16
         else:
             proj = self.hm["proj"]
             mean = ops.token_mean_fwd(x_f32.view(B, S, H))
@@ -397,6 +405,8 @@ class BertTower(_Tower):
                 linear_wgrad(dhpre, state["x_top"], [td.weight], [td.bias], grads, **_ordered(det))
             dx = torch.empty((M, H), dtype=F32, device=dev)
             ops.gemm_nt(dhpre, wt_t, out_f32=dx)
+        elif self.head_kind == "hidden":
+            dx = dout   # [M,H], bf16 or fp32: the top layer's LayerNorm backward takes either
         else:
             proj = self.hm["proj"]
             dmean = dense_head_backward(dout, state["mean"], proj.weight, proj.bias, grads, out_bf16=False, **_ordered(det))
