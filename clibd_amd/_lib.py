@@ -203,6 +203,14 @@ MLM_SIGNATURES = {
     "clibd_mlm_ce_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# baseline JPEG decode on the device (include/clibd_hip_jpeg.h): an eleventh additive table, bound after the other ten
+JPEG_SIGNATURES = {
+    "clibd_jpeg_plan": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "clibd_jpeg_workspace_bytes": (c_size_t, [C.c_int64]),
+    "clibd_jpeg_decode_u8": (c_int, [c_void_p, C.c_int64, c_void_p, c_int, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, c_size_t, C.c_int64, c_int,
+                                     c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7  # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -228,7 +236,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items())
                               + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(INSECT_SIGNATURES.items()) + list(MLP_SIGNATURES.items())
-                              + list(ATTN_WIDE_SIGNATURES.items()) + list(MLM_SIGNATURES.items())):
+                              + list(ATTN_WIDE_SIGNATURES.items()) + list(MLM_SIGNATURES.items()) + list(JPEG_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

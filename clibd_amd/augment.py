@@ -9,6 +9,10 @@ The random parameters follow torchvision's samplers in distribution (not stream 
 DataLoader workers): `draw_uniforms` draws them in bulk from a seeded torch.Generator, `params_from_uniforms` turns them into crop
 boxes, flips and angles.  A packed batch is a dict of tensors {"data", "offsets", "xforms"}, so `data.DevicePrefetcher` moves it as it
 is; `apply` turns it into fp32 [B,3,224,224] on the device without a host synchronisation.
+
+With decode="device" (opt-in) the baseline JPEG streams of a batch stay compressed on the host: the batch is {"jpeg", "plans", "offsets",
+"host_pixels", "xforms"}, and `apply` decodes them with HIP kernels (clibd_jpeg_decode_u8, csrc/jpeg.hip) into the same packed
+pixels, equal to PIL's byte for byte, with a host synchronisation on the decode's status word (`decode_packed`).
 """
 from __future__ import annotations
 
@@ -198,16 +202,7 @@ def decode_images(encoded, lengths=None, threads: Optional[int] = None, pin: Opt
 
     encoded: a list of `bytes`, or the reference's HDF5 layout (`image` uint8 [B, Lmax] zero-padded, `lengths` = its `image_mask`).
     Returns (data uint8 [N] (pinned when a GPU is present), offsets int64 [B+1], sizes int64 [B, 2] = (H, W))."""
-    if lengths is not None:
-        enc = np.asarray(encoded.cpu() if torch.is_tensor(encoded) else encoded, dtype=np.uint8)
-        lens = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
-        if enc.ndim != 2 or len(enc) != len(lens) or (lens < 0).any() or (lens > enc.shape[1]).any():
-            raise ValueError("decode_images: image [B, Lmax] with one length in [0, Lmax] per row expected")
-        bufs = [enc[i, :lens[i]] for i in range(len(lens))]
-    else:
-        bufs = list(encoded)
-    if not bufs:
-        raise ValueError("decode_images: empty batch")
+    bufs = _buffers(encoded, lengths, "decode_images")
     nthreads = max(1, min(MAX_THREADS, threads or default_threads()))
     with cf.ThreadPoolExecutor(max_workers=nthreads) as ex:
         arrays = list(ex.map(_decode_one, bufs))
@@ -225,8 +220,159 @@ def decode_images(encoded, lengths=None, threads: Optional[int] = None, pin: Opt
     return data, torch.from_numpy(offsets), torch.from_numpy(sizes)
 
 
-def pack(encoded, train: bool, generator: Optional[torch.Generator] = None, lengths=None, threads: Optional[int] = None) -> dict:
-    """Decoded, packed batch with its records: {"data", "offsets", "xforms"} (see module doc)."""
+# ---- decode on the device -------------------------------------------------------------------------------------------------------------
+# Baseline JPEG streams are planned on the host (clibd_jpeg_plan: markers, tables, H and W; no GPU) and decoded by HIP kernels
+# (clibd_jpeg_decode_u8, csrc/jpeg.hip) into the same packed buffer; every other stream takes `_decode_one`.  DESIGN §3.15.
+PLAN_BYTES = 4096                # struct clibd_jpeg_record (include/clibd_hip_jpeg.h)
+_PLAN_HEAD = np.dtype([("reason", "<i4"), ("H", "<i4"), ("W", "<i4"), ("sampling", "<i4"), ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("blocks", "<i4"),
+                       ("restart_interval", "<i4"), ("scan_begin", "<i4"), ("stream_len", "<i4"), ("stream_begin", "<i8"), ("coef_begin", "<i8")])
+_PLAN = np.dtype(_PLAN_HEAD.descr + [("tables", "u1", (PLAN_BYTES - _PLAN_HEAD.itemsize,))])
+assert _PLAN_HEAD.itemsize == 56 and _PLAN.itemsize == PLAN_BYTES
+DECODERS = ("host", "device")
+
+
+def _check_decode(decode: str) -> bool:
+    if decode not in DECODERS:
+        raise ValueError(f"augment: decode must be one of {DECODERS}, not {decode!r}")
+    return decode == "device"
+
+
+def _buffers(encoded, lengths, who: str) -> list:
+    if lengths is not None:
+        enc = np.asarray(encoded.cpu() if torch.is_tensor(encoded) else encoded, dtype=np.uint8)
+        lens = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
+        if enc.ndim != 2 or len(enc) != len(lens) or (lens < 0).any() or (lens > enc.shape[1]).any():
+            raise ValueError(f"{who}: image [B, Lmax] with one length in [0, Lmax] per row expected")
+        bufs = [enc[i, :lens[i]] for i in range(len(lens))]
+    else:
+        bufs = list(encoded)
+    if not bufs:
+        raise ValueError(f"{who}: empty batch")
+    return bufs
+
+
+def plan_streams(bufs, threads: Optional[int] = None) -> np.ndarray:
+    """One struct clibd_jpeg_record per stream (a numpy record array [B] of PLAN_BYTES each), placement fields zero.  Host only."""
+    import ctypes
+
+    from . import _lib
+
+    lib = _lib.load()
+    plans = np.zeros(len(bufs), dtype=_PLAN)
+    base = plans.ctypes.data
+
+    def one(i):
+        b = bufs[i]
+        a = np.frombuffer(b, dtype=np.uint8) if isinstance(b, (bytes, bytearray, memoryview)) else np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+        if lib.clibd_jpeg_plan(ctypes.c_void_p(a.ctypes.data if a.size else None), a.size, ctypes.c_void_p(base + i * PLAN_BYTES)) < 0:
+            raise RuntimeError("clibd_jpeg_plan failed")   # a null record: cannot happen here
+
+    nthreads = max(1, min(MAX_THREADS, threads or default_threads()))
+    with cf.ThreadPoolExecutor(max_workers=nthreads) as ex:
+        list(ex.map(one, range(len(bufs))))
+    return plans
+
+
+def _pack_device(bufs, threads: Optional[int] = None, pin: Optional[bool] = None):
+    """The device-decode form of a batch, made without touching the GPU: ({"jpeg", "plans", "offsets", "host_pixels"}, sizes).
+    Streams the plan does not call eligible are decoded here with `_decode_one` (its exceptions included)."""
+    plans = plan_streams(bufs, threads)
+    B = len(bufs)
+    device_idx = np.nonzero(plans["reason"] == 0)[0]
+    host_idx = np.nonzero(plans["reason"] != 0)[0]
+    nthreads = max(1, min(MAX_THREADS, threads or default_threads()))
+    with cf.ThreadPoolExecutor(max_workers=nthreads) as ex:
+        arrays = list(ex.map(lambda i: _decode_one(bufs[i]), host_idx))
+    sizes = np.stack([plans["H"], plans["W"]], axis=1).astype(np.int64)
+    for i, a in zip(host_idx, arrays):
+        sizes[i] = a.shape[:2]
+    offsets = _packed_offsets(sizes)
+    if pin is None:
+        pin = torch.cuda.is_available()
+    lens = np.array([len(bufs[i]) for i in device_idx], dtype=np.int64)
+    begin = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    jpeg = torch.empty((int(begin[-1]),), dtype=torch.uint8, pin_memory=bool(pin and begin[-1] > 0))
+    flat = jpeg.numpy()
+    for k, i in enumerate(device_idx):
+        flat[begin[k]:begin[k + 1]] = np.frombuffer(bufs[i], dtype=np.uint8) if isinstance(bufs[i], (bytes, bytearray, memoryview)) else bufs[i]
+    plans["stream_begin"][device_idx] = begin[:-1]
+    blocks = np.where(plans["reason"] == 0, plans["blocks"], 0).astype(np.int64)
+    plans["coef_begin"] = np.concatenate([[0], np.cumsum(blocks)])[:B]
+    nhost = int(sum(a.size for a in arrays))
+    host_pixels = torch.empty((nhost,), dtype=torch.uint8, pin_memory=bool(pin and nhost > 0))
+    if arrays:
+        host_pixels.numpy()[:] = np.concatenate([a.reshape(-1) for a in arrays])
+    packed = {"jpeg": jpeg, "plans": torch.from_numpy(plans.view(np.uint8).reshape(B, PLAN_BYTES)), "offsets": torch.from_numpy(offsets),
+              "host_pixels": host_pixels}
+    return packed, torch.from_numpy(sizes)
+
+
+def is_device_packed(image) -> bool:
+    return isinstance(image, dict) and "jpeg" in image and "plans" in image and "offsets" in image
+
+
+def decode_packed(packed: dict, device=None, return_status: bool = False):
+    """The pixels of a device-decode batch: uint8 [N] on the device, the layout `decode_images` returns.  Copies the compressed bytes,
+    launches the decode, copies the host-decoded slices in, reads the status word once and decodes again with `_decode_one` every image
+    the device gave up on (a damaged file then behaves as on the host path, PIL's exception included).  return_status: also the int32 [B]
+    status as the device left it (0: decoded there; a plan's reason: decoded on the host from the start; >= 32: stopped on the device and
+    decoded again on the host).  Host synchronisations: the status read after the launch; and, when the batch's tensors were moved to the
+    device beforehand (a prefetcher), two small reads before it, of the records' 56-byte heads and of the offsets."""
+    from . import ops
+
+    if device is None:
+        device = packed["jpeg"].device if packed["jpeg"].is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    plans = packed["plans"]
+    B = plans.shape[0]
+    head = plans[:, :_PLAN_HEAD.itemsize].cpu().contiguous().numpy().view(_PLAN_HEAD).reshape(B)
+    offsets = packed["offsets"].cpu().numpy()
+    on_device = head["reason"] == 0
+    out = torch.empty((int(offsets[-1]),), dtype=torch.uint8, device=device)
+    status = None
+    jpeg = packed["jpeg"].to(device, non_blocking=True)
+    if on_device.any():
+        total_blocks = int(head["blocks"][on_device].astype(np.int64).sum())
+        status = ops.jpeg_decode(jpeg, plans.to(device, non_blocking=True), packed["offsets"].to(device, non_blocking=True), out, total_blocks)
+    host_pixels = packed["host_pixels"].to(device, non_blocking=True)
+    at = 0
+    for i in np.nonzero(~on_device)[0]:
+        n = int(offsets[i + 1] - offsets[i])
+        out[int(offsets[i]):int(offsets[i + 1])].copy_(host_pixels[at:at + n])
+        at += n
+    st = np.where(on_device, 0, head["reason"]).astype(np.int32)
+    if status is not None:
+        st = status.cpu().numpy()                                   # the synchronisation after the launch
+        for i in np.nonzero(on_device & (st != 0))[0]:
+            b0 = int(head["stream_begin"][i])
+            a = _decode_one(packed["jpeg"][b0:b0 + int(head["stream_len"][i])].cpu().numpy())
+            if a.shape[:2] != (int(head["H"][i]), int(head["W"][i])):
+                raise ValueError("decode_images: the image's size differs from its frame header")
+            out[int(offsets[i]):int(offsets[i + 1])].copy_(torch.from_numpy(a.reshape(-1).copy()))
+    return (out, torch.from_numpy(st)) if return_status else out
+
+
+def decode_images_device(encoded, lengths=None, device=None, threads: Optional[int] = None, return_status: bool = False):
+    """`decode_images` with the baseline JPEG streams decoded on the device: (data uint8 [N] on the device, offsets int64 [B+1],
+    sizes int64 [B, 2]), equal to `decode_images`'s byte for byte.  Takes both of its input layouts.  return_status: a fourth entry,
+    `decode_packed`'s status (which images the device decoded itself)."""
+    packed, sizes = _pack_device(_buffers(encoded, lengths, "decode_images"), threads)
+    if return_status:
+        data, status = decode_packed(packed, device, return_status=True)
+        return data, packed["offsets"], sizes, status
+    return decode_packed(packed, device), packed["offsets"], sizes
+
+
+def pack(encoded, train: bool, generator: Optional[torch.Generator] = None, lengths=None, threads: Optional[int] = None,
+         decode: str = "host") -> dict:
+    """Decoded, packed batch with its records: {"data", "offsets", "xforms"} (see module doc).  decode="device": the batch with its
+    baseline JPEG streams still compressed, {"jpeg", "plans", "offsets", "host_pixels", "xforms"}, made without touching the GPU;
+    `apply` decodes it there."""
+    if _check_decode(decode):
+        packed, sizes = _pack_device(_buffers(encoded, lengths, "decode_images"), threads)
+        offsets = packed["offsets"]
+        packed["xforms"] = sample_train_params(sizes, generator, offsets[:-1]) if train else eval_params(sizes, offsets[:-1])
+        return packed
     data, offsets, sizes = decode_images(encoded, lengths=lengths, threads=threads)
     xforms = sample_train_params(sizes, generator, offsets[:-1]) if train else eval_params(sizes, offsets[:-1])
     return {"data": data, "offsets": offsets, "xforms": xforms}
@@ -244,19 +390,20 @@ def _stack(items):
     return list(items)
 
 
-def collate_encoded(samples, train: bool, generator: Optional[torch.Generator] = None, threads: Optional[int] = None):
+def collate_encoded(samples, train: bool, generator: Optional[torch.Generator] = None, threads: Optional[int] = None, decode: str = "host"):
     """collate_fn for the reference's 7-tuples whose image entry is the ENCODED image (bytes): returns the reference's batch
-    (processid, image, dna, input_ids, token_type_ids, attention_mask, label) with image = {"data", "offsets", "xforms"}.
+    (processid, image, dna, input_ids, token_type_ids, attention_mask, label) with image = {"data", "offsets", "xforms"}, or with
+    decode="device" the form `pack` documents (no GPU is touched here: the function runs in loader workers).
     Labels are stacked into a tensor (training) or gathered into {level: [labels]} (eval label dicts), as default_collate does."""
     cols = list(zip(*samples))
     if len(cols) != 7:
         raise ValueError("collate_encoded: samples must be the reference's 7-tuples")
-    image = pack(list(cols[1]), train, generator, threads=threads)
+    image = pack(list(cols[1]), train, generator, threads=threads, decode=decode)
     return (list(cols[0]), image, _stack(cols[2]), _stack(cols[3]), _stack(cols[4]), _stack(cols[5]), _stack(cols[6]))
 
 
 def is_packed(image) -> bool:
-    return isinstance(image, dict) and "data" in image and "xforms" in image
+    return isinstance(image, dict) and ("data" in image or is_device_packed(image)) and "xforms" in image
 
 
 def apply(packed: dict, device=None) -> torch.Tensor:
@@ -264,6 +411,9 @@ def apply(packed: dict, device=None) -> torch.Tensor:
     enqueued on the current stream, no host synchronisation."""
     from . import ops
 
+    if is_device_packed(packed):     # decode="device": a host synchronisation on the decode's status word (see decode_packed)
+        data = decode_packed(packed, device)
+        return ops.image_transform(data, packed["xforms"].to(data.device, non_blocking=True))
     if device is None:
         device = packed["data"].device if packed["data"].is_cuda else torch.device("cuda", torch.cuda.current_device())
     return ops.image_transform(packed["data"].to(device, non_blocking=True), packed["xforms"].to(device, non_blocking=True))

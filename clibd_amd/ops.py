@@ -966,6 +966,33 @@ def image_transform(data: torch.Tensor, xforms: torch.Tensor, workspace: Optiona
     return out
 
 
+def jpeg_decode(streams: torch.Tensor, plans: torch.Tensor, offsets: torch.Tensor, out: torch.Tensor, total_blocks: int,
+                status: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, phases: int = 3) -> torch.Tensor:
+    """Baseline JPEG decode on the device (clibd_jpeg_decode_u8): `streams` uint8 [n] (the eligible streams, packed), `plans` uint8
+    [B, 4096] (struct clibd_jpeg_record, built by clibd_amd.augment), `offsets` int64 [>= B] -> RGB HWC uint8 pixels of image i at
+    out[offsets[i]:].  Returns the int32 [B] status (0: decoded; otherwise the slice is zero, or untouched for a record the plan left to
+    the host).  phases: 1 entropy decode, 2 reconstruction, 3 both.  The kernels read and write nothing outside the buffers given here
+    whatever the streams and records hold."""
+    for t, dt, name in ((streams, torch.uint8, "streams"), (plans, torch.uint8, "plans"), (offsets, I64, "offsets"), (out, torch.uint8, "out")):
+        _chk(t, dt, name)
+        if t.device != out.device:
+            raise ValueError("jpeg_decode: every tensor must be on one device")
+    if plans.dim() != 2 or plans.shape[1] != 4096 or plans.shape[0] == 0 or offsets.numel() < plans.shape[0]:
+        raise ValueError("jpeg_decode: plans must be uint8 [B, 4096] with one offset per image")
+    B = plans.shape[0]
+    lib = _lib.load()
+    need = int(lib.clibd_jpeg_workspace_bytes(int(total_blocks)))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=out.device)
+    if status is None:
+        status = torch.empty((B,), dtype=I32, device=out.device)
+    _chk(status, I32, "status")
+    check(lib.clibd_jpeg_decode_u8(streams.data_ptr(), streams.numel(), plans.data_ptr(), B, out.data_ptr(), out.numel(), offsets.data_ptr(),
+                                   status.data_ptr(), workspace.data_ptr(), workspace.numel(), int(total_blocks), int(phases), _stream()),
+          "jpeg_decode_u8")
+    return status
+
+
 def simclr_views(data: torch.Tensor, xforms: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Packed RGB HWC uint8 pixels `data` [N] + one record per view `xforms` int32 [n, 16] (struct clibd_view_xform; built by
     clibd_amd.simclr_views) -> fp32 [n,3,224,224]: crop / flip / colour jitter / grayscale / blur of the SimCLR pipeline

@@ -20,7 +20,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .augment import ATTEMPTS, _packed_offsets, _randint, _sizes, crop_box, decode_images
+from .augment import (ATTEMPTS, _buffers, _check_decode, _pack_device, _packed_offsets, _randint, _sizes, crop_box, decode_images, decode_packed,
+                      is_device_packed)
 
 BOX_MAX = 3584                      # crop box side the kernel accepts (224 x 16: at most 34 filter taps per output row / column)
 FLAG_HFLIP, FLAG_JITTER, FLAG_GRAY = 1, 2, 4
@@ -133,21 +134,27 @@ def sample_view_params(sizes, generator: Optional[torch.Generator] = None, offse
 
 
 # ---- decode, pack, apply ------------------------------------------------------------------------------------------------------------
-def pack_two_views(encoded, generator: Optional[torch.Generator] = None, lengths=None, threads: Optional[int] = None) -> dict:
+def pack_two_views(encoded, generator: Optional[torch.Generator] = None, lengths=None, threads: Optional[int] = None,
+                   decode: str = "host") -> dict:
     """Decoded, packed batch with the records of its 2B views: {"data", "offsets", "xforms"} (see module doc).  Every image is decoded
-    once and serves both of its views.  `encoded` / `lengths`: as `augment.decode_images` takes them."""
+    once and serves both of its views.  `encoded` / `lengths`: as `augment.decode_images` takes them.  decode="device": the form
+    `augment.pack` documents, {"jpeg", "plans", "offsets", "host_pixels", "xforms"}, made without touching the GPU."""
+    if _check_decode(decode):
+        packed, sizes = _pack_device(_buffers(encoded, lengths, "decode_images"), threads)
+        packed["xforms"] = sample_view_params(sizes, generator, packed["offsets"][:-1])
+        return packed
     data, offsets, sizes = decode_images(encoded, lengths=lengths, threads=threads)
     return {"data": data, "offsets": offsets, "xforms": sample_view_params(sizes, generator, offsets[:-1])}
 
 
-def collate_two_views(samples, generator: Optional[torch.Generator] = None, threads: Optional[int] = None) -> dict:
+def collate_two_views(samples, generator: Optional[torch.Generator] = None, threads: Optional[int] = None, decode: str = "host") -> dict:
     """collate_fn for a dataset whose items are ENCODED images (bytes; the reference's `DatasetForSimCLRStyleTraining.load_image`
     input): returns the packed batch `SimCLR.train_step` takes."""
-    return pack_two_views(list(samples), generator, threads=threads)
+    return pack_two_views(list(samples), generator, threads=threads, decode=decode)
 
 
 def is_packed(batch) -> bool:
-    return isinstance(batch, dict) and "data" in batch and "xforms" in batch
+    return isinstance(batch, dict) and ("data" in batch or is_device_packed(batch)) and "xforms" in batch
 
 
 def apply(packed: dict, device=None) -> torch.Tensor:
@@ -155,6 +162,9 @@ def apply(packed: dict, device=None) -> torch.Tensor:
     copied first, asynchronously from pinned memory); enqueued on the current stream, no host synchronisation."""
     from . import ops
 
+    if is_device_packed(packed):     # decode="device": a host synchronisation on the decode's status word (augment.decode_packed)
+        data = decode_packed(packed, device)
+        return ops.simclr_views(data, packed["xforms"].to(data.device, non_blocking=True))
     if device is None:
         device = packed["data"].device if packed["data"].is_cuda else torch.device("cuda", torch.cuda.current_device())
     return ops.simclr_views(packed["data"].to(device, non_blocking=True), packed["xforms"].to(device, non_blocking=True))
