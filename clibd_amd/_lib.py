@@ -211,6 +211,14 @@ JPEG_SIGNATURES = {
                                      c_void_p]),
 }
 
+# masked-LM labels: compaction and BERT's sampler (include/clibd_hip_mlm_labels.h): a twelfth additive table, bound after the other eleven
+MLM_LABELS_SIGNATURES = {
+    "clibd_mlm_compact_workspace_bytes": (c_size_t, [c_int]),
+    "clibd_mlm_compact_labels": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_mlm_mask_bert": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int64, c_void_p, c_int,
+                                    c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7  # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -236,7 +244,8 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items())
                               + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(INSECT_SIGNATURES.items()) + list(MLP_SIGNATURES.items())
-                              + list(ATTN_WIDE_SIGNATURES.items()) + list(MLM_SIGNATURES.items()) + list(JPEG_SIGNATURES.items())):
+                              + list(ATTN_WIDE_SIGNATURES.items()) + list(MLM_SIGNATURES.items()) + list(JPEG_SIGNATURES.items())
+                              + list(MLM_LABELS_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

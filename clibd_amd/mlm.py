@@ -1,8 +1,9 @@
 """Masked-k-mer pre-training of the BarcodeBERT DNA tower on the MI355X HIP engine: the link between a collection of barcodes and the
 checkpoint `load_pre_trained_bioscan_bert` reads (`bioscan_bert_checkpoint`), as `clibd_amd.simclr` is for the image tower.
 
-The objective is HF `BertForMaskedLM(input_ids, labels)` — what the reference instantiates (model/dna_encoder.py:35-37) — with labels =
--100 outside the masked positions: mean cross-entropy over the masked k-mers.  The tower is `clibd_amd.towers.BertTower` under full
+The objective is HF `BertForMaskedLM(input_ids, attention_mask, labels).loss` — what the reference instantiates (model/dna_encoder.py:35-37)
+— with labels = -100 outside the masked positions: mean cross-entropy over the masked k-mers.  Two call forms: the project's own
+`model(masked_ids, rows, targets, n_valid)`, and HF's `model(input_ids=, attention_mask=, labels=, label_capacity=)` (below).  The tower is `clibd_amd.towers.BertTower` under full
 fine-tuning with head="hidden" (post-LN stack, embedding gradients, train-mode dropout, deterministic mode: all the DNA tower's); the
 vocabulary head runs on the MASKED rows only: gather -> transform dense + GELU -> LayerNorm -> decoder GEMM to bf16 logits -> the fused
 cross-entropy of csrc/mlm.hip, which leaves the gradient in the logits' place; the backward is the mirror and ends in a scatter into the
@@ -14,14 +15,36 @@ seed), s) and the n_mask smallest keys are chosen, so padding k-mers are taken o
 its target the original id, or -100 where that was unk_id.  BarcodeBERT's own training code is not part of the reference, so this rule is
 this project's and is pinned by the restatement in tests/mlm_reference.py.
 
+HF-style labels.  `labels [B, S]` int64 with -100 = ignore and any number of labelled positions per sequence (position 0 and padded
+positions included) are compacted on the device (csrc/mlm_labels.hip) into the ascending `rows` / `targets` the head runs on.  The
+number of labelled rows is data, the head's GEMMs need a row count on the host, and nothing synchronises: the head runs at a capacity
+R_cap, a multiple of 64 in 64 .. B S rounded up (`label_capacity`; None = B S rounded up, always enough).  The tail is padding: row
+index -1 (gathered as zeros, never scattered), target -100 (zero loss, zero logit gradient).  More labelled positions than R_cap set the
+sticky device word `model.label_overflow` and leave the first R_cap rows: a caller that passes a capacity must check that word
+(`pretrain_epoch` does, in its one host fetch, and raises); nothing is truncated silently.  The loss divides by the number of labelled
+positions, as HF's mean does.
+
+The attention mask.  `attention_mask [B, S]`, nonzero = a live key, becomes the tower's int32 key mask and reaches the 64-wide masked
+attention kernels in the forward and the backward, with and without dropout.  HF's semantics: a masked key gets probability 0; the
+query rows of padded positions are still computed and matter only if labelled.  Every sequence must have at least position 0 live; an
+all-zero row gives what the masked attention kernels define for it, which is not HF's result.  Towers with 128- or 192-wide heads raise
+NotSupportedYet when a mask is passed (their kernels take full sequences only) and take labels and both samplers without one.
+
+The 80/10/10 sampler (csrc/mlm_labels.hip, `mask_tokens_bert`): with i = b S + s, T(p) = floor(p 2^32 + 0.5) as a 64-bit integer and
+u0 = lowbias32(i ^ seed), u1 = lowbias32(u0 + 0x9E3779B9), u2 = lowbias32(u0 + 2 * 0x9E3779B9) (mod 2^32): a position is eligible iff
+s >= 1, its mask entry is nonzero and its id is no special id; it is chosen iff eligible and u0 < T(mlm_probability); a chosen id
+becomes mask_id if u1 < T(replace[0]), else len(special_ids) + ((u2 (V - len(special_ids))) >> 32) — a uniform non-special id — if
+u1 < T(replace[0]) + T(replace[1]), else stays; labels = the original id where chosen, -100 elsewhere.  A pure function of (seed, i):
+no launch shape enters.  replace = (1, 0, 0) is plain masking.  Pinned by the numpy restatement in tests/mlm_labels_reference.py.
+
 One stated divergence from a default-configured HF model: BertConfig's default pad_token_id = 0 is this vocabulary's <MASK>, which makes
 row 0 of HF's word table an nn.Embedding padding row whose lookup gradient torch drops.  The embedding backward here has no padding row
 (it never had one): the mask token's embedding trains through the lookup like every other row, as an HF model built with
 pad_token_id=None does (the golden's models are built so).
 
 Out of scope (each raises or simply does not exist here):
-  - HF-style `labels [B, S]` with a free number of masked positions per sequence: every sequence has exactly n_mask rows;
-  - 80/10/10 replacement (a chosen position always becomes mask_id), whole-word or span masking;
+  - whole-word or span masking (the fixed-count sampler always writes mask_id; 80/10/10 replacement is `mask_tokens_bert`'s);
+  - HF-style `labels [B, S]` beyond 2^24 positions, and an attention mask that is not [B, S] (no per-query or per-head masks);
   - the remote-code tokenizer of the newer BarcodeBERT checkpoints (strings go through the k-mer kernel, `eval.tokenize_barcodes`);
   - data-parallel pre-training (the flat gradient bucket is one all-reduce message, but nothing here issues it and it is unmeasured);
   - fp8 modes for this step;
@@ -60,12 +83,43 @@ def mask_tokens(ids: torch.Tensor, mask_ratio: float = 0.5, seed: Optional[int] 
     return ops.mlm_mask(ids.to(torch.int64).contiguous(), seed, n_mask_for(ids.shape[1], mask_ratio), mask_id, unk_id)
 
 
+def mask_tokens_bert(ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, mlm_probability: float = 0.15, seed: Optional[int] = None,
+                     mask_id: int = 0, special_ids=(0, 1, 2), replace=(0.8, 0.1, 0.1), vocab_size=None):
+    """BERT's sampler with 80/10/10 replacement (the module docstring has the rule): ids int64 [B, S] on the device -> (masked_ids,
+    labels), both int64 [B, S] on the device, labels = -100 off the chosen positions.  Never chosen: position 0, positions with a zero
+    attention_mask, ids in special_ids.  vocab_size: the vocabulary size V, or the model to take it from; it may be left out only when
+    replace[1] == 0 (no random replacement is ever drawn).  seed=None draws it from the CPU generator, as `mask_tokens` does."""
+    if ids.dim() != 2:
+        raise ValueError("mask_tokens_bert: ids must be [B, S]")
+    if vocab_size is None:
+        if replace[1] != 0:
+            raise ValueError("mask_tokens_bert: random replacement needs vocab_size (an int, or the model)")
+        V = len(special_ids) + 1
+    elif isinstance(vocab_size, int):
+        V = vocab_size
+    else:
+        V = vocab_size.bert.embeddings.word_embeddings.weight.shape[0]
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+    return ops.mlm_mask_bert(ids.to(torch.int64).contiguous(), attention_mask, V, seed, mlm_probability, mask_id, special_ids, replace)
+
+
+def barcode_attention_mask(ids: torch.Tensor, unk_id: int = 2) -> torch.Tensor:
+    """The attention mask of N-padded barcodes, int32 [B, S] on ids' device: a barcode shorter than the batch's window is padded with N,
+    whose k-mers are <UNK>, so the TRAILING run of <UNK> ids of a sequence is its padding and everything before it is live — an <UNK>
+    inside the barcode (an ambiguous base) stays a live key, as in the reference's tokenizer, which pads after tokenizing.  Position 0
+    is always live."""
+    live = (ids != unk_id).flip(1).to(torch.int32).cummax(dim=1).values.flip(1)
+    live[:, 0] = 1
+    return live.contiguous()
+
+
 class _MLMFn(torch.autograd.Function):
-    """forward(owner, masked_ids, rows, targets, n_valid, *trainable parameters) -> (loss, correct)"""
+    """forward(owner, masked_ids, rows, targets, n_valid, key_mask, *trainable parameters) -> (loss, correct)"""
 
     @staticmethod
-    def forward(ctx, owner, masked_ids, rows, targets, n_valid, *params):
-        loss, correct, state = owner._forward(masked_ids, rows, targets, n_valid, True)
+    def forward(ctx, owner, masked_ids, rows, targets, n_valid, key_mask, *params):
+        loss, correct, state = owner._forward(masked_ids, rows, targets, n_valid, True, key_mask)
         ctx.owner, ctx.state, ctx.nparams = owner, state, len(params)
         ctx.mark_non_differentiable(correct)
         return loss, correct
@@ -81,10 +135,10 @@ class _MLMFn(torch.autograd.Function):
         sink = owner.grad_sink
         if sink is not None and all(id(p) in sink for p in params):
             owner._backward(dloss, state, sink)   # the optimizer's flat bucket (clibd_amd.optim.FusedAdamW): accumulate straight into it
-            return (None,) * (5 + len(params))
+            return (None,) * (6 + len(params))
         bucket = GradBucket(params)
         owner._backward(dloss, state, bucket.views)
-        return (None, None, None, None, None, *bucket.ordered())
+        return (None, None, None, None, None, None, *bucket.ordered())
 
 
 class BarcodeBERTForPreTraining(nn.Module):
@@ -118,6 +172,16 @@ class BarcodeBERTForPreTraining(nn.Module):
             p.requires_grad_(True)
         self.grad_sink = None   # {id(param): fp32 accumulation tensor}: see attach()
         self._tower = None
+        self._label_overflow = None
+
+    @property
+    def label_overflow(self) -> torch.Tensor:
+        """int32 [1] on the parameters' device, sticky: bit 0 is set once an HF-style call met more labelled positions than its capacity.
+        Reading it is a host synchronisation; `.zero_()` re-arms it."""
+        dev = self.bert.embeddings.word_embeddings.weight.device
+        if self._label_overflow is None or self._label_overflow.device != dev:
+            self._label_overflow = torch.zeros((1,), dtype=torch.int32, device=dev)
+        return self._label_overflow
 
     def tower(self) -> BertTower:
         if self._tower is None:
@@ -152,21 +216,46 @@ class BarcodeBERTForPreTraining(nn.Module):
                 ps.append(p)
         return ps
 
-    def forward(self, masked_ids, rows, targets, n_valid):
-        """(loss fp32 scalar, correct int32 [1]) on the device; under autograd `loss.backward()` produces every parameter gradient."""
+    def forward(self, masked_ids=None, rows=None, targets=None, n_valid=None, *, input_ids=None, attention_mask=None, labels=None,
+                label_capacity: Optional[int] = None):
+        """(loss fp32 scalar, correct int32 [1]) on the device; under autograd `loss.backward()` produces every parameter gradient.
+        Two forms:
+          model(masked_ids, rows, targets, n_valid)          the sampler's rows (`mask_tokens`);
+          model(input_ids=, attention_mask=, labels=, label_capacity=)     HF's: labels int64 [B, S], -100 = ignore, any number of labelled
+              positions per sequence; the loss is the mean cross-entropy over them.  label_capacity: the row capacity of the head, a
+              multiple of 64 in 64 .. B S rounded up; None = B S rounded up, which always suffices.  A caller that passes a smaller one
+              must check `model.label_overflow` (a device tensor, sticky): when more positions are labelled the first `label_capacity`
+              of them are used and that word is set; no host synchronisation happens here.
+        attention_mask ([B, S], nonzero = a live key; either form): HF's semantics, every sequence with at least position 0 live; 64-wide
+        heads only (wider towers raise NotSupportedYet)."""
+        if labels is not None or input_ids is not None:
+            if labels is None or input_ids is None or any(a is not None for a in (masked_ids, rows, targets, n_valid)):
+                raise TypeError("BarcodeBERTForPreTraining: pass either (masked_ids, rows, targets, n_valid) or input_ids= and labels=")
+            if input_ids.dim() != 2 or tuple(labels.shape) != tuple(input_ids.shape):
+                raise ValueError("BarcodeBERTForPreTraining: input_ids and labels must both be [B, S]")
+            V = self.bert.embeddings.word_embeddings.weight.shape[0]
+            masked_ids = input_ids
+            rows, targets, n_valid = ops.mlm_compact_labels(labels.to(torch.int64).contiguous(), V, label_capacity, overflow=self.label_overflow)
+        elif label_capacity is not None:
+            raise TypeError("BarcodeBERTForPreTraining: label_capacity belongs to the labels= form")
+        key_mask = None
+        if attention_mask is not None:
+            if tuple(attention_mask.shape) != tuple(masked_ids.shape):
+                raise ValueError("BarcodeBERTForPreTraining: attention_mask must be [B, S]")
+            key_mask = (attention_mask != 0).to(torch.int32).contiguous()
         params = self.trainable_params()
         if torch.is_grad_enabled() and params:
-            return _MLMFn.apply(self, masked_ids, rows, targets, n_valid, *params)
+            return _MLMFn.apply(self, masked_ids, rows, targets, n_valid, key_mask, *params)
         with torch.no_grad():
-            loss, correct, _ = self._forward(masked_ids, rows, targets, n_valid, False)
+            loss, correct, _ = self._forward(masked_ids, rows, targets, n_valid, False, key_mask)
         return loss, correct
 
-    def _forward(self, masked_ids, rows, targets, n_valid, save):
+    def _forward(self, masked_ids, rows, targets, n_valid, save, key_mask=None):
         tw = self.tower()
         tw.training = self.training
         if tw.stack.fp8 is not None:
             raise NotSupportedYet("BarcodeBERTForPreTraining: the fp8 forward")
-        x_top, state = tw._forward((masked_ids, None, None), save)   # [M, H] bf16
+        x_top, state = tw._forward((masked_ids, None, key_mask), save)   # [M, H] bf16
         loss, correct, head = self._head_forward(x_top, rows, targets, n_valid)
         if save:
             state.update(mlm=head)
@@ -245,7 +334,7 @@ def _ids_of(batch, device, k: int) -> torch.Tensor:
         from .eval import tokenize_barcodes
 
         return tokenize_barcodes(list(batch), device, k=k)
-    raise TypeError("pre-training batches are int64 [b, S] token ids or lists of barcode strings")
+    raise TypeError("pre-training batches are int64 [b, S] token ids, (ids, attention_mask) pairs or lists of barcode strings")
 
 
 def _kmer_k(model) -> int:
@@ -256,24 +345,58 @@ def _kmer_k(model) -> int:
     raise NotSupportedYet(f"a vocabulary of {V} entries is not <MASK>, <CLS>, <UNK> + 4^k k-mers: pass token ids")
 
 
-def pretrain_step(model: BarcodeBERTForPreTraining, batch, optimizer, mask_ratio: float = 0.5, seed: Optional[int] = None):
-    """mask -> forward -> backward -> optimizer step on one batch (token ids or barcode strings); returns the device tensors
-    (loss, correct, n_valid).  No host synchronisation."""
+def pretrain_step(model: BarcodeBERTForPreTraining, batch, optimizer, mask_ratio: float = 0.5, seed: Optional[int] = None, sampler: str = "fixed",
+                  mlm_probability: float = 0.15, attention_mask: Optional[torch.Tensor] = None, label_capacity: Optional[int] = None):
+    """mask -> forward -> backward -> optimizer step on one batch; returns the device tensors (loss, correct, n_valid).  No host
+    synchronisation.
+    batch: token ids int64 [b, S], a pair (ids, attention_mask), or a list of barcode strings.
+    sampler="fixed" (the default): `mask_tokens` at `mask_ratio`, exactly n_mask rows per sequence; an attention mask, if one is given,
+        reaches the encoder; barcode strings get none (as before).
+    sampler="bert": `mask_tokens_bert` at `mlm_probability` with 80/10/10 replacement and HF-style labels.  Barcode strings get the
+        mask of `barcode_attention_mask` (the trailing <UNK> run of a sequence is padding).  label_capacity=None: ceil(b S min(1, p +
+        6 sqrt(p (1 - p) / (b S)))) rounded up to 64 — six binomial standard deviations over the mean.  Overflow sets
+        `model.label_overflow`; `pretrain_epoch` raises on it."""
+    if sampler not in ("fixed", "bert"):
+        raise ValueError('pretrain_step: sampler is "fixed" or "bert"')
     dev = next(model.parameters()).device
-    ids = _ids_of(batch, dev, _kmer_k(model) if not isinstance(batch, torch.Tensor) else 0)
-    masked, rows, targets, n_valid = mask_tokens(ids, mask_ratio, seed)
+    strings = False
+    if isinstance(batch, (list, tuple)) and len(batch) == 2 and all(isinstance(t, torch.Tensor) for t in batch):
+        if attention_mask is not None:
+            raise TypeError("pretrain_step: an attention mask in the batch and another as an argument")
+        batch, attention_mask = batch
+    elif not isinstance(batch, torch.Tensor):
+        strings = True
+    ids = _ids_of(batch, dev, _kmer_k(model) if strings else 0)
+    if attention_mask is not None:
+        attention_mask = attention_mask.to(dev)
     optimizer.zero_grad()
-    loss, correct = model(masked, rows, targets, n_valid)
+    if sampler == "fixed":
+        if label_capacity is not None:
+            raise TypeError('pretrain_step: label_capacity belongs to sampler="bert"')
+        masked, rows, targets, n_valid = mask_tokens(ids, mask_ratio, seed)
+        loss, correct = model(masked, rows, targets, n_valid, attention_mask=attention_mask)
+    else:
+        if strings and attention_mask is None:
+            attention_mask = barcode_attention_mask(ids)
+        masked, labels = mask_tokens_bert(ids, attention_mask, mlm_probability, seed, vocab_size=model)
+        if label_capacity is None:
+            label_capacity = ops.mlm_label_capacity(ids.numel(), mlm_probability)
+        V = model.bert.embeddings.word_embeddings.weight.shape[0]   # what model(input_ids=, labels=) does, keeping the count for the caller
+        rows, targets, n_valid = ops.mlm_compact_labels(labels, V, label_capacity, overflow=model.label_overflow)
+        loss, correct = model(masked, rows, targets, n_valid, attention_mask=attention_mask)
     loss.backward()
     optimizer.step()
     return loss.detach(), correct, n_valid
 
 
-def pretrain_epoch(model: BarcodeBERTForPreTraining, loader, optimizer, scheduler=None, mask_ratio: float = 0.5, log_every: int = 0):
-    """One pass over `loader` (int64 [b, S] ids or lists of barcode strings) in train mode.  `optimizer`: clibd_amd.optim.FusedAdamW over
+def pretrain_epoch(model: BarcodeBERTForPreTraining, loader, optimizer, scheduler=None, mask_ratio: float = 0.5, log_every: int = 0,
+                   sampler: str = "fixed", mlm_probability: float = 0.15, label_capacity: Optional[int] = None):
+    """One pass over `loader` (int64 [b, S] ids, (ids, attention_mask) pairs or lists of barcode strings) in train mode; `sampler`,
+    `mlm_probability` and `label_capacity` as in `pretrain_step`.  `optimizer`: clibd_amd.optim.FusedAdamW over
     model.parameters(), wired to the backward here as simclr.py wires its own; `scheduler` (optional) is stepped per batch.  The loss and
     the masked-token hits accumulate on the device and are fetched once, at the end (log_every > 0 fetches the running mean every that many
-    steps, a host synchronisation each).  Returns {"loss": mean step loss, "accuracy": hits / valid targets, "steps": n}."""
+    steps, a host synchronisation each); the same fetch reads `model.label_overflow` and raises RuntimeError if a step met more labelled
+    positions than its capacity.  Returns {"loss": mean step loss, "accuracy": hits / valid targets, "steps": n}."""
     if hasattr(optimizer, "flat_g"):
         model.attach(optimizer)
     model.train()
@@ -281,7 +404,8 @@ def pretrain_epoch(model: BarcodeBERTForPreTraining, loader, optimizer, schedule
     acc = torch.zeros((3,), dtype=torch.float64, device=dev)   # sum of step losses, hits, valid targets
     n = 0
     for batch in loader:
-        loss, correct, n_valid = pretrain_step(model, batch, optimizer, mask_ratio)
+        loss, correct, n_valid = pretrain_step(model, batch, optimizer, mask_ratio, sampler=sampler, mlm_probability=mlm_probability,
+                                               label_capacity=label_capacity)
         acc += torch.stack([loss.double(), correct[0].double(), n_valid[0].double()])
         n += 1
         if scheduler is not None:
@@ -289,7 +413,11 @@ def pretrain_epoch(model: BarcodeBERTForPreTraining, loader, optimizer, schedule
         if log_every and n % log_every == 0:
             s = acc.tolist()
             print(f"step {n}\tloss {s[0] / n:.4f}\tmasked-token accuracy {s[1] / max(s[2], 1.0):.4f}")
-    s = acc.tolist()   # the one host fetch of the epoch
+    s = torch.cat([acc, model.label_overflow.double()]).tolist()   # the one host fetch of the epoch
+    if s[3] != 0:
+        model.label_overflow.zero_()
+        raise RuntimeError("pretrain_epoch: a step labelled more positions than its label_capacity (model.label_overflow): rows were left "
+                           "out of the loss; rerun with a larger capacity or label_capacity=None")
     return {"loss": s[0] / max(n, 1), "accuracy": s[1] / max(s[2], 1.0), "steps": n}
 
 

@@ -1729,3 +1729,87 @@ def mlm_ce_(logits: torch.Tensor, V: int, targets: torch.Tensor, n_valid: torch.
     check(_lib.load().clibd_mlm_ce_bf16(logits.data_ptr(), ld, targets.data_ptr(), R, V, n_valid.data_ptr(), row_loss.data_ptr(), loss.data_ptr(),
                                         correct.data_ptr(), ce_error_word(dev).data_ptr(), _stream()), "mlm_ce_bf16")
     return loss, correct, row_loss
+
+
+# ---- masked-LM labels: compaction and BERT's sampler (include/clibd_hip_mlm_labels.h) ---------------------------------------------------------
+MLM_PAD_ROW = -1   # CLIBD_MLM_PAD_ROW: rows_gather reads a zero row for it, rows_scatter writes nothing
+_mlm_overflow = {}
+
+
+def mlm_overflow_word(device) -> torch.Tensor:
+    """The device word mlm_compact_labels ORs its overflow bit into unless the caller passes its own.  Sticky; reading it is a host
+    synchronisation, so nothing on the training path does."""
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    w = _mlm_overflow.get(dev)
+    if w is None:
+        w = _mlm_overflow[dev] = torch.zeros((1,), dtype=I32, device=dev)
+    return w
+
+
+def mlm_label_capacity(M: int, p: Optional[float] = None) -> int:
+    """The row capacity of the vocabulary head for M = B * S positions, a multiple of 64.  p=None: M rounded up (always enough).  A
+    probability p: M * min(1, p + 6 sqrt(p (1 - p) / M)) rounded up — six binomial standard deviations over the mean number of chosen
+    positions when every one of the M is eligible."""
+    M = int(M)
+    if M < 1:
+        raise ValueError("mlm_label_capacity: M must be positive")
+    full = (M + 63) // 64 * 64
+    if p is None:
+        return full
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("mlm_label_capacity: p must be in [0, 1]")
+    n = math.ceil(M * min(1.0, p + 6.0 * math.sqrt(p * (1.0 - p) / M)))
+    return min(full, max(64, (n + 63) // 64 * 64))
+
+
+def mlm_compact_labels(labels: torch.Tensor, V: int, r_cap: Optional[int] = None, overflow: Optional[torch.Tensor] = None):
+    """HF-style labels int64 [...] (MLM_IGNORE = not labelled) -> (rows int32 [r_cap], targets int64 [r_cap], n_labelled int32 [1])
+    (clibd_mlm_compact_labels): the labelled flat positions ascending, then padding (MLM_PAD_ROW / MLM_IGNORE).  r_cap: a multiple of 64
+    in 64 .. M rounded up; None = M rounded up.  More labelled positions than r_cap set bit 0 of `overflow` (int32 [1], sticky; default
+    mlm_overflow_word) and leave the correct prefix; a label outside [0, V) sets bit 0 of ce_error_word.  Nothing is read back."""
+    _chk(labels, I64, "labels")
+    M = labels.numel()
+    r_cap = mlm_label_capacity(M) if r_cap is None else int(r_cap)
+    if M < 1 or M > 1 << 24 or r_cap < 64 or r_cap % 64 or r_cap > (M + 63) // 64 * 64 or int(V) < 1:
+        raise ValueError("mlm_compact_labels: need 1 <= M <= 2^24, V >= 1 and r_cap a multiple of 64 in 64 .. M rounded up to 64")
+    dev = labels.device
+    if overflow is None:
+        overflow = mlm_overflow_word(dev)
+    else:
+        _chk(overflow, I32, "overflow")
+    L = _lib.load()
+    rows = torch.empty((r_cap,), dtype=I32, device=dev)
+    targets = torch.empty((r_cap,), dtype=I64, device=dev)
+    n = torch.empty((1,), dtype=I32, device=dev)
+    ws = torch.empty((L.clibd_mlm_compact_workspace_bytes(M),), dtype=torch.uint8, device=dev)
+    check(L.clibd_mlm_compact_labels(labels.data_ptr(), M, int(V), r_cap, rows.data_ptr(), targets.data_ptr(), n.data_ptr(), overflow.data_ptr(),
+                                     ce_error_word(dev).data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "mlm_compact_labels")
+    return rows, targets, n
+
+
+def mlm_mask_bert(ids: torch.Tensor, attention_mask: Optional[torch.Tensor], V: int, seed: int, mlm_probability: float = 0.15, mask_id: int = 0,
+                  special_ids=(0, 1, 2), replace=(0.8, 0.1, 0.1)):
+    """BERT's Bernoulli sampler (clibd_mlm_mask_bert; the header has the rule): ids int64 [B, S], attention_mask [B, S] or None ->
+    (masked int64 [B, S], labels int64 [B, S]).  `replace` = (P mask_id, P random non-special id, P unchanged), summing to 1."""
+    _chk(ids, I64, "ids")
+    if ids.dim() != 2:
+        raise ValueError("mlm_mask_bert: ids must be [B, S]")
+    B, S = ids.shape
+    special = [int(s) for s in special_ids]
+    if len(replace) != 3 or abs(sum(replace) - 1.0) > 1e-6 or min(replace) < 0:
+        raise ValueError("mlm_mask_bert: replace = (mask, random, unchanged), non-negative, summing to 1")
+    if B < 1 or S < 1 or len(special) > 8 or int(V) <= len(special) or not 0.0 <= mlm_probability <= 1.0:
+        raise ValueError("mlm_mask_bert: need B, S >= 1, at most 8 special ids, V > their number and a probability in [0, 1]")
+    am = None
+    if attention_mask is not None:
+        if tuple(attention_mask.shape) != (B, S) or not attention_mask.is_cuda:
+            raise ValueError("mlm_mask_bert: attention_mask must be a device tensor [B, S]")
+        am = attention_mask.to(I32).contiguous()
+    masked, labels = torch.empty_like(ids), torch.empty_like(ids)
+    sp = (C.c_int64 * max(len(special), 1))(*special)
+    check(_lib.load().clibd_mlm_mask_bert(ids.data_ptr(), _p(am), B, S, int(V), int(seed) & 0xFFFFFFFF, float(mlm_probability), float(replace[0]),
+                                          float(replace[1]), int(mask_id), C.cast(sp, C.c_void_p), len(special), masked.data_ptr(), labels.data_ptr(),
+                                          _stream()), "mlm_mask_bert")
+    return masked, labels
