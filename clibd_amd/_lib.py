@@ -219,6 +219,23 @@ MLM_LABELS_SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p]),
 }
 
+# gradient norm, clipping, skip and the grouped update (include/clibd_hip_optim.h): a thirteenth additive table, bound after the other twelve
+class OptimGroup(C.Structure):
+    """Mirror of `struct clibd_optim_group` (include/clibd_hip_optim.h)."""
+
+    _fields_ = [("first", c_size_t), ("lr", c_float), ("weight_decay", c_float)]
+
+
+OPTIM_MAX_GROUPS = 8     # CLIBD_OPTIM_MAX_GROUPS
+OPTIM_SIGNATURES = {
+    "clibd_grad_norm_workspace_bytes": (c_size_t, [c_size_t]),
+    "clibd_grad_norm": (c_int, [c_void_p, c_size_t, c_float, c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "clibd_adamw_step_groups": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_float, c_float, c_float, c_int, c_float,
+                                        c_void_p, c_void_p]),
+    "clibd_adam_l2_step_groups": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_float, c_float, c_float, c_int, c_float,
+                                          c_void_p, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7  # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -245,7 +262,7 @@ def load() -> C.CDLL:
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items())
                               + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(INSECT_SIGNATURES.items()) + list(MLP_SIGNATURES.items())
                               + list(ATTN_WIDE_SIGNATURES.items()) + list(MLM_SIGNATURES.items()) + list(JPEG_SIGNATURES.items())
-                              + list(MLM_LABELS_SIGNATURES.items())):
+                              + list(MLM_LABELS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -108,8 +108,9 @@ def _optimizer_layout(model: torch.nn.Module, optimizer) -> list:
     fix_temperature and on the backward order (train._backward_order), so the raw flat moments alone do not say which
     parameter a slice belongs to."""
     names = {id(p): n for n, p in model.named_parameters()}
-    return [(names.get(id(p), f"<unnamed {i}>"), int(off), int(p.numel()))
-            for i, (p, off) in enumerate(zip(optimizer.param_groups[0]["params"], optimizer._offsets))]
+    # every group, in bucket order (optim.FusedAdamW.bucket_params; a stand-in without it is walked group by group, which is the same order)
+    params = optimizer.bucket_params() if hasattr(optimizer, "bucket_params") else [p for g in optimizer.param_groups for p in g["params"]]
+    return [(names.get(id(p), f"<unnamed {i}>"), int(off), int(p.numel())) for i, (p, off) in enumerate(zip(params, optimizer._offsets))]
 
 
 def save_training_state(path: str, model: torch.nn.Module, optimizer=None, scheduler=None, epoch: Optional[int] = None):
@@ -159,6 +160,9 @@ def load_training_state(path: str, model: torch.nn.Module, optimizer=None, sched
                 optimizer.exp_avg[off : off + k].copy_(o["exp_avg"][s_off : s_off + k])
                 optimizer.exp_avg_sq[off : off + k].copy_(o["exp_avg_sq"][s_off : s_off + k])
         optimizer.step_count = o["step_count"]
+        if len(o["param_groups"]) != len(optimizer.param_groups):
+            raise ValueError(f"training state has {len(o['param_groups'])} optimizer parameter groups, this optimizer {len(optimizer.param_groups)}: "
+                             "their hyperparameters cannot be matched")
         for g, saved_g in zip(optimizer.param_groups, o["param_groups"]):
             g.update(saved_g)
         # the flat parameter bucket aliases the parameters, which load_state_dict just overwrote in place

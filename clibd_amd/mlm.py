@@ -199,7 +199,7 @@ class BarcodeBERTForPreTraining(nn.Module):
         """wire a clibd_amd.optim.FusedAdamW built over `self.parameters()`: the backward accumulates into its flat gradient bucket"""
         if not hasattr(optimizer, "flat_g"):
             raise NotSupportedYet("BarcodeBERTForPreTraining.attach: needs clibd_amd.optim.FusedAdamW (the flat gradient bucket)")
-        self.grad_sink = {id(p): p.grad for p in optimizer.param_groups[0]["params"]}
+        self.grad_sink = {id(p): p.grad for p in optimizer.bucket_params()}
         return self
 
     def _head(self):
@@ -396,13 +396,17 @@ def pretrain_epoch(model: BarcodeBERTForPreTraining, loader, optimizer, schedule
     model.parameters(), wired to the backward here as simclr.py wires its own; `scheduler` (optional) is stepped per batch.  The loss and
     the masked-token hits accumulate on the device and are fetched once, at the end (log_every > 0 fetches the running mean every that many
     steps, a host synchronisation each); the same fetch reads `model.label_overflow` and raises RuntimeError if a step met more labelled
-    positions than its capacity.  Returns {"loss": mean step loss, "accuracy": hits / valid targets, "steps": n}."""
+    positions than its capacity, and `optimizer.skipped_steps` (clibd_amd.optim, nonfinite="skip").  Returns {"loss": mean step loss,
+    "accuracy": hits / valid targets, "steps": n, "skipped": steps this epoch dropped for a non-finite gradient norm (0 for an optimizer
+    without the counter)}.  A skipped step still counts in "steps" and its loss still enters the mean, so a NaN loss shows there."""
     if hasattr(optimizer, "flat_g"):
         model.attach(optimizer)
     model.train()
     dev = next(model.parameters()).device
     acc = torch.zeros((3,), dtype=torch.float64, device=dev)   # sum of step losses, hits, valid targets
     n = 0
+    counter = getattr(optimizer, "skipped_steps", None)
+    skipped0 = counter.clone() if counter is not None else torch.zeros((1,), dtype=torch.int32, device=dev)   # a device copy, no fetch
     for batch in loader:
         loss, correct, n_valid = pretrain_step(model, batch, optimizer, mask_ratio, sampler=sampler, mlm_probability=mlm_probability,
                                                label_capacity=label_capacity)
@@ -413,12 +417,13 @@ def pretrain_epoch(model: BarcodeBERTForPreTraining, loader, optimizer, schedule
         if log_every and n % log_every == 0:
             s = acc.tolist()
             print(f"step {n}\tloss {s[0] / n:.4f}\tmasked-token accuracy {s[1] / max(s[2], 1.0):.4f}")
-    s = torch.cat([acc, model.label_overflow.double()]).tolist()   # the one host fetch of the epoch
+    skipped = (counter if counter is not None else skipped0) - skipped0
+    s = torch.cat([acc, model.label_overflow.double(), skipped.double()]).tolist()   # the one host fetch of the epoch
     if s[3] != 0:
         model.label_overflow.zero_()
         raise RuntimeError("pretrain_epoch: a step labelled more positions than its label_capacity (model.label_overflow): rows were left "
                            "out of the loss; rerun with a larger capacity or label_capacity=None")
-    return {"loss": s[0] / max(n, 1), "accuracy": s[1] / max(s[2], 1.0), "steps": n}
+    return {"loss": s[0] / max(n, 1), "accuracy": s[1] / max(s[2], 1.0), "steps": n, "skipped": int(s[4])}
 
 
 def bert_config_of(model) -> dict:

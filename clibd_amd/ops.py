@@ -848,6 +848,54 @@ def adam_l2_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_sca
                                          float(eps), float(weight_decay), int(step), float(grad_scale), _stream()), "adam_l2_step")
 
 
+def grad_norm_workspace(n: int, device) -> torch.Tensor:
+    nbytes = _lib.load().clibd_grad_norm_workspace_bytes(int(n))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
+def grad_norm(g: torch.Tensor, record: torch.Tensor, ws: torch.Tensor, grad_scale: float = 1.0, max_norm: Optional[float] = None,
+              skip_nonfinite: bool = False) -> None:
+    """The L2 norm of the flat fp32 gradient `g` times `grad_scale`, in a fixed order (include/clibd_hip_optim.h).  `record` is a 16-byte
+    device buffer the caller zeroed once, int32 [4]: [0] the norm and [1] the clip coefficient as fp32 bits (`record.view(torch.float32)`),
+    [2] skip_now, [3] the running count of skips.  max_norm=None: no clipping (coefficient 1)."""
+    _chk(g, F32, "g")
+    _chk(record, torch.int32, "record")
+    if g.dim() != 1 or record.numel() != 4:
+        raise ValueError("grad_norm: g is flat, record is int32 [4]")
+    check(_lib.load().clibd_grad_norm(g.data_ptr(), g.numel(), float(grad_scale), 0.0 if max_norm is None else float(max_norm),
+                                      int(bool(skip_nonfinite)), record.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "grad_norm")
+
+
+def _step_groups(entry, what, p, g, m, v, groups, beta1, beta2, eps, step, grad_scale, record):
+    import ctypes
+
+    for nm, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        _chk(t, F32, nm)
+    n = p.numel()
+    if g.numel() != n or m.numel() != n or v.numel() != n:
+        raise ValueError(f"{what}: size mismatch")
+    if record is not None:
+        _chk(record, torch.int32, "record")
+        if record.numel() != 4:
+            raise ValueError(f"{what}: record is int32 [4]")
+    groups = list(groups)
+    table = (_lib.OptimGroup * max(len(groups), 1))(*[_lib.OptimGroup(int(f), float(lr), float(wd)) for f, lr, wd in groups])
+    check(entry(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, ctypes.cast(table, ctypes.c_void_p), len(groups), float(beta1),
+                float(beta2), float(eps), int(step), float(grad_scale), _p(record), _stream()), what)
+
+
+def adamw_step_groups(p, g, m, v, groups, beta1, beta2, eps, step, grad_scale=1.0, record=None) -> None:
+    """`adamw_step` with per-group hyperparameters and the clip / skip record of `grad_norm`: `groups` is a list of at most 8
+    (first element, lr, weight_decay), first ascending from 0 in multiples of 64; the gradient is g * (grad_scale * coef); a set skip flag
+    leaves p, m and v untouched.  record=None: no clipping, no skip.  The table travels in the kernel arguments: no copy to the device."""
+    _step_groups(_lib.load().clibd_adamw_step_groups, "adamw_step_groups", p, g, m, v, groups, beta1, beta2, eps, step, grad_scale, record)
+
+
+def adam_l2_step_groups(p, g, m, v, groups, beta1, beta2, eps, step, grad_scale=1.0, record=None) -> None:
+    """`adam_l2_step` with per-group hyperparameters and the clip / skip record (see `adamw_step_groups`)."""
+    _step_groups(_lib.load().clibd_adam_l2_step_groups, "adam_l2_step_groups", p, g, m, v, groups, beta1, beta2, eps, step, grad_scale, record)
+
+
 def ntxent_workspace(N: int, D: int, device) -> torch.Tensor:
     nbytes = _lib.load().clibd_ntxent_workspace_bytes(N, D)
     return torch.empty((nbytes,), dtype=torch.uint8, device=device)

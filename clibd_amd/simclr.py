@@ -172,7 +172,7 @@ class SimCLR(object):
             if self._dist:
                 self.optimizer.grad_scale = 1.0 / torch.distributed.get_world_size()   # SUM all-reduce, then DDP's mean
             if hasattr(self.model, "tower"):
-                self.model.tower().grad_sink = {id(p): p.grad for p in self.optimizer.param_groups[0]["params"]}
+                self.model.tower().grad_sink = {id(p): p.grad for p in self.optimizer.bucket_params()}
         elif self._dist:
             raise NotSupportedYet("SimCLR: data-parallel training needs clibd_amd.optim.FusedAdam (the flat gradient bucket is the all-reduce message)")
 

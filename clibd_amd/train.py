@@ -71,7 +71,8 @@ class Trainer:
     def __init__(self, model, lr: float = 1e-3, world_size: int = 1, rank: int = 0, all_gather: bool = True,
                  fix_temperature: Optional[float] = None, bind_to=None, no_image_text_loss=False, weight_decay: float = 1e-2,
                  broadcast_parameters: bool = True, bucket_bytes: int = 64 << 20, fp8_recalibrate_every: int = 0,
-                 numerics: Optional[dict] = None, deterministic: Optional[bool] = None):
+                 numerics: Optional[dict] = None, deterministic: Optional[bool] = None, max_grad_norm: Optional[float] = None,
+                 nonfinite: str = "propagate"):
         """bucket_bytes: at world_size > 1, when the gradients are at least two buckets long (full fine-tune: 694 MB), the
         all-reduce is issued in pieces of about this size as the backward completes them, each on the stream that produced
         it, so RCCL runs under the rest of the backward; smaller gradient sets (LoRA: 6 MB) keep the single all-reduce.
@@ -81,7 +82,10 @@ class Trainer:
         numerics: backward arithmetic switches for every tower of `model` (clibd_amd.engine.NUMERICS_CHOICES); None keeps what the
         towers were constructed with (environment defaults).
         deterministic: True / False turns the deterministic training mode on / off on every tower (SimpleCLIP.set_deterministic: fixed-order
-        reductions, a step repeats bit for bit on one GPU; RCCL's all-reduce order across ranks is not covered); None keeps the model's setting."""
+        reductions, a step repeats bit for bit on one GPU; RCCL's all-reduce order across ranks is not covered); None keeps the model's setting.
+        max_grad_norm, nonfinite: handed to the FusedAdamW (clibd_amd.optim): global-norm clipping of the all-reduced, averaged gradient and
+        the device-side skip of a step whose norm is inf or NaN; `self.optimizer.grad_norm` / `.skipped_steps` are device tensors.  The
+        norm is summed in a fixed order in every mode.  The defaults keep the single plain update launch."""
         self.model, self.world_size, self.rank = model, world_size, rank
         if numerics:    # e.g. dict(residual_grad="fp32"): the reference's fp32 residual-gradient stream (engine.NUMERICS_CHOICES)
             model.set_numerics(**numerics)
@@ -92,7 +96,7 @@ class Trainer:
         self.fix_temperature = fix_temperature
         self.fp8_recalibrate_every, self._steps_done = int(fp8_recalibrate_every), 0
         ordered, counts = _backward_order(model, _gradient_reachable(model, fix_temperature))
-        self.optimizer = FusedAdamW(ordered, lr=lr, weight_decay=weight_decay)
+        self.optimizer = FusedAdamW(ordered, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, nonfinite=nonfinite)
         self._plan_buckets(counts, bucket_bytes)
         if all_gather:
             self.criterion = ClipLoss(local_loss=False, gather_with_grad=True, rank=rank, world_size=world_size,
@@ -107,7 +111,7 @@ class Trainer:
             # replaced decoder are randomly initialised per process.  Trainable values live in the flat bucket (one message);
             # frozen weights and buffers follow tensor by tensor (once, at start-up).
             dist.broadcast(self.optimizer.flat_p, src=0)
-            own = {id(p) for p in self.optimizer.param_groups[0]["params"]}
+            own = {id(p) for p in self.optimizer.bucket_params()}
             with torch.no_grad():
                 for t in list(model.parameters()) + list(model.buffers()):
                     if id(t) not in own:
@@ -118,7 +122,7 @@ class Trainer:
                 if hasattr(tw, "invalidate_weight_images"):
                     tw.invalidate_weight_images()
         # let the towers accumulate parameter gradients straight into the optimizer's flat bucket
-        sink = {id(p): p.grad for p in self.optimizer.param_groups[0]["params"]}
+        sink = {id(p): p.grad for p in self.optimizer.bucket_params()}
         for ti, tw in enumerate(_towers(model)):
             tw.grad_sink = sink
             if self._bucketed:
