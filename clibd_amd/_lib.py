@@ -236,6 +236,12 @@ OPTIM_SIGNATURES = {
                                           c_void_p, c_void_p]),
 }
 
+# gradient accumulation: the norm with a device divisor (include/clibd_hip_accum.h): a fourteenth additive table, bound after the other thirteen
+ACCUM_SIGNATURES = {
+    "clibd_grad_norm_div_workspace_bytes": (c_size_t, [c_size_t]),
+    "clibd_grad_norm_div": (c_int, [c_void_p, c_size_t, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 _lib = None
 ABI_VERSION = 7  # what this binding was written against (clibd_abi_version(), csrc/capi.hip); load() refuses any other library
 
@@ -262,7 +268,7 @@ def load() -> C.CDLL:
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VIEW_SIGNATURES.items()) + list(CLS_SIGNATURES.items())
                               + list(ANALYSIS_SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(INSECT_SIGNATURES.items()) + list(MLP_SIGNATURES.items())
                               + list(ATTN_WIDE_SIGNATURES.items()) + list(MLM_SIGNATURES.items()) + list(JPEG_SIGNATURES.items())
-                              + list(MLM_LABELS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items())):
+                              + list(MLM_LABELS_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(ACCUM_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

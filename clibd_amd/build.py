@@ -21,13 +21,13 @@ INCLUDE = HERE.parent / "include"
 LIB = HERE / "libclibd_hip.so"
 OBJ = CSRC / "build"
 ARCH = "gfx950"
-SOURCES = ["capi", "gemm", "gemm256", "gemm256_tn", "layernorm", "attention", "attention_wide", "lora", "elementwise", "loss", "topk", "paramgrad", "evalacc", "augment", "ntxent", "views", "split3", "classifier", "analysis", "prototypes", "mlp", "jpeg", "optim", "mlm_labels", "mlm", "rollout"]
+SOURCES = ["capi", "gemm", "gemm256", "gemm256_tn", "layernorm", "attention", "attention_wide", "lora", "elementwise", "loss", "topk", "paramgrad", "evalacc", "augment", "ntxent", "views", "split3", "classifier", "analysis", "prototypes", "mlp", "jpeg", "optim", "accum", "mlm_labels", "mlm", "rollout"]
 
 
 def _public_headers() -> list[Path]:
     """the C-ABI headers: clibd_hip.h and the additive ones beside it (clibd_hip_simclr.h, clibd_hip_views.h, clibd_hip_classifier.h,
     clibd_hip_analysis.h, clibd_hip_rollout.h, clibd_hip_insect.h, clibd_hip_mlp.h, clibd_hip_attn_wide.h, clibd_hip_mlm.h, clibd_hip_jpeg.h,
-    clibd_hip_mlm_labels.h, clibd_hip_optim.h)"""
+    clibd_hip_mlm_labels.h, clibd_hip_optim.h, clibd_hip_accum.h)"""
     return sorted(INCLUDE.glob("clibd_hip*.h"))
 
 

@@ -114,6 +114,9 @@ def _optimizer_layout(model: torch.nn.Module, optimizer) -> list:
 
 
 def save_training_state(path: str, model: torch.nn.Module, optimizer=None, scheduler=None, epoch: Optional[int] = None):
+    if optimizer is not None and getattr(optimizer, "window_open", False):
+        raise ValueError("save_training_state: the optimizer is in the middle of an accumulation window (its bucket holds gradients that no "
+                         "update has applied): call optimizer.flush() or finish the window first")
     state = {"model": model.state_dict(), "epoch": epoch}
     if hasattr(model, "numerics"):
         state["numerics"] = model.numerics()   # which arithmetic produced these weights (engine.NUMERICS_CHOICES + fp8-forward flag)

@@ -14,13 +14,10 @@
 #include "../../include/clibd_hip.h"
 #include "../../include/clibd_hip_optim.h"
 #include "host_util.h"
+#include "grad_norm_pass1.h"
 
 namespace clibd {
 
-constexpr int OPT_THREADS = 256;
-constexpr int OPT_WAVES = 4;
-constexpr int NORM_F4_PER_THREAD = 16;
-constexpr int NORM_CHUNK = OPT_THREADS * NORM_F4_PER_THREAD * 4;
 static_assert(NORM_CHUNK == CLIBD_GRAD_NORM_CHUNK, "the chunk is part of the ABI");
 
 struct GroupTable {
@@ -32,28 +29,7 @@ struct GroupTable {
 
 __global__ __launch_bounds__(OPT_THREADS) void grad_sumsq_kernel(const float* __restrict__ g, size_t n, float* __restrict__ partials) {
     __shared__ float wave_tot[OPT_WAVES];
-    const size_t base = (size_t)blockIdx.x * NORM_CHUNK;
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < NORM_F4_PER_THREAD; ++k) {
-        const size_t i = base + ((size_t)k * OPT_THREADS + threadIdx.x) * 4;
-        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i + 3 < n) {
-            x = *(const float4*)(g + i);
-        } else {   // the bucket's last float4, cut short by n
-            if (i < n) x.x = g[i];
-            if (i + 1 < n) x.y = g[i + 1];
-            if (i + 2 < n) x.z = g[i + 2];
-        }
-        acc = fmaf(x.x, x.x, acc);
-        acc = fmaf(x.y, x.y, acc);
-        acc = fmaf(x.z, x.z, acc);
-        acc = fmaf(x.w, x.w, acc);
-    }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = ((wave_tot[0] + wave_tot[1]) + wave_tot[2]) + wave_tot[3];
+    grad_sumsq_chunk(g, n, partials, wave_tot);   // grad_norm_pass1.h: the one source of pass 1, shared with accum.hip
 }
 
 __global__ __launch_bounds__(OPT_THREADS) void grad_norm_finish_kernel(const float* __restrict__ partials, unsigned chunks, float grad_scale,
@@ -145,8 +121,6 @@ __global__ __launch_bounds__(OPT_THREADS) void adam_groups_kernel(float* __restr
         }
     }
 }
-
-static inline size_t norm_chunks(size_t n) { return (n + NORM_CHUNK - 1) / NORM_CHUNK; }
 
 template <bool L2>
 static int step_groups(const char* op, float* p, const float* g, float* m, float* v, size_t n, const clibd_optim_group* groups, int n_groups,

@@ -46,10 +46,30 @@ Out of scope (each raises or simply does not exist here):
   - whole-word or span masking (the fixed-count sampler always writes mask_id; 80/10/10 replacement is `mask_tokens_bert`'s);
   - HF-style `labels [B, S]` beyond 2^24 positions, and an attention mask that is not [B, S] (no per-query or per-head masks);
   - the remote-code tokenizer of the newer BarcodeBERT checkpoints (strings go through the k-mer kernel, `eval.tokenize_barcodes`);
-  - data-parallel pre-training (the flat gradient bucket is one all-reduce message, but nothing here issues it and it is unmeasured);
+  - data-parallel pre-training over RCCL on more than one GPU is unmeasured (data-parallel pre-training itself: below and §3.18);
   - fp8 modes for this step;
   - S > 256 (S > 192 with 192-wide heads), and an attention mask with wide heads: full sequences only, as the towers.
 The upstream gradient of the loss is taken as a device scalar; the loss's own gradient is written by the forward's cross-entropy kernel.
+
+Large batches: gradient accumulation and data-parallel.  `pretrain_step` / `pretrain_epoch(..., accumulation_steps=k,
+world_size=W, rank=r)` make k micro-batches on each of W ranks ONE update, the update of the batch k W times the size, exactly:
+  - sum mode inside a window.  The cross-entropy gets a device word holding 1 as n_valid, so a micro-batch's loss is the SUM of its row
+    losses and its gradient the sum's; the real count, that loss sum and the hits are added on the device into three spare slots of the
+    optimizer's bucket (`aux[AUX_COUNT]`, `aux[AUX_LOSS]`, `aux[AUX_HITS]`).  Counts travel as fp32: exact up to 2^24 labelled positions
+    per window, which is not checked;
+  - the window's divisor is the GLOBAL labelled count (`optimizer.divisor_slot = AUX_COUNT`, `ops.grad_norm_div`): a token-weighted mean over
+    all micro-batches and ranks — what one big batch computes, and what recent HF versions compute through `num_items_in_batch`.  It
+    differs from DDP's mean of per-rank means (and from the classic mean of micro-batch means) whenever the counts differ;
+  - data parallel: once per window, after the closing backward, ONE `dist.all_reduce(optimizer.flat_comm)` (SUM) carries gradients, count,
+    loss sum and hits; grad_scale = 1; no other collective per step.  `pretrain_epoch` broadcasts rank 0's `flat_p` at its start and
+    invalidates the tower's weight images, as `train.Trainer` does.  Sharding the data is the caller's job (DistributedSampler, as in the
+    reference).  Over RCCL on more than one GPU this path is unmeasured;
+  - mask seeds and dropout bases differ between ranks and micro-steps: both come from `micro_seed(seed, rank, micro-step)` (seed=None: a
+    value drawn from the CPU generator, the same on equally seeded ranks); the tower draws its dropout base from a forked CPU generator
+    seeded with it;
+  - `scheduler.step()` runs once per applied window, `optimizer.flush()` at the epoch's end; the returned loss is sum of row losses / sum
+    of counts over the whole epoch and all ranks, "steps" counts updates.
+With k = 1 and W = 1 every launch, the returned dict and every bit of the parameters are what they were.  `evaluate` scores a held-out set.
 """
 from __future__ import annotations
 
@@ -345,52 +365,164 @@ def _kmer_k(model) -> int:
     raise NotSupportedYet(f"a vocabulary of {V} entries is not <MASK>, <CLS>, <UNK> + 4^k k-mers: pass token ids")
 
 
-def pretrain_step(model: BarcodeBERTForPreTraining, batch, optimizer, mask_ratio: float = 0.5, seed: Optional[int] = None, sampler: str = "fixed",
-                  mlm_probability: float = 0.15, attention_mask: Optional[torch.Tensor] = None, label_capacity: Optional[int] = None):
-    """mask -> forward -> backward -> optimizer step on one batch; returns the device tensors (loss, correct, n_valid).  No host
-    synchronisation.
-    batch: token ids int64 [b, S], a pair (ids, attention_mask), or a list of barcode strings.
-    sampler="fixed" (the default): `mask_tokens` at `mask_ratio`, exactly n_mask rows per sequence; an attention mask, if one is given,
-        reaches the encoder; barcode strings get none (as before).
-    sampler="bert": `mask_tokens_bert` at `mlm_probability` with 80/10/10 replacement and HF-style labels.  Barcode strings get the
-        mask of `barcode_attention_mask` (the trailing <UNK> run of a sequence is padding).  label_capacity=None: ceil(b S min(1, p +
-        6 sqrt(p (1 - p) / (b S)))) rounded up to 64 — six binomial standard deviations over the mean.  Overflow sets
-        `model.label_overflow`; `pretrain_epoch` raises on it."""
-    if sampler not in ("fixed", "bert"):
-        raise ValueError('pretrain_step: sampler is "fixed" or "bert"')
+AUX_COUNT, AUX_LOSS, AUX_HITS = 1, 2, 3   # slots of FusedAdamW.aux (slot 0 is train.Trainer's loss): labelled count, loss sum, hits, fp32
+_ones = {}
+
+
+def _one(dev) -> torch.Tensor:
+    """a device int32 [1] holding 1: as the cross-entropy's n_valid it turns the mean into the sum (never written)"""
+    dev = torch.device(dev)
+    if dev not in _ones:
+        _ones[dev] = torch.ones((1,), dtype=torch.int32, device=dev)
+    return _ones[dev]
+
+
+def micro_seed(seed: int, rank: int, micro_step: int) -> int:
+    """the 31-bit seed of micro-step `micro_step` on rank `rank`: lowbias32 over the three values chained, so that neither two ranks
+    nor two micro-steps share a mask or a dropout pattern.  A pure function (tests restate the masks from it)."""
+    x = int(seed) & 0xFFFFFFFF
+    for v in (int(rank) + 1, int(micro_step) + 1):
+        x = (x ^ (v * 0x9E3779B1)) & 0xFFFFFFFF
+        x ^= x >> 16
+        x = (x * 0x7FEB352D) & 0xFFFFFFFF
+        x ^= x >> 15
+        x = (x * 0x846CA68B) & 0xFFFFFFFF
+        x ^= x >> 16
+    return x & 0x7FFFFFFF
+
+
+def _batch_inputs(model, batch, attention_mask, labels, who: str):
+    """(ids on the device, attention_mask on the device or None, labels or None, whether the batch was barcode strings).  A dict is an
+    HF collator's batch: "input_ids", and optionally "attention_mask" and "labels"."""
     dev = next(model.parameters()).device
     strings = False
-    if isinstance(batch, (list, tuple)) and len(batch) == 2 and all(isinstance(t, torch.Tensor) for t in batch):
+    if isinstance(batch, dict):
+        if (attention_mask is not None and batch.get("attention_mask") is not None) or (labels is not None and batch.get("labels") is not None):
+            raise TypeError(f"{who}: an attention mask or labels in the batch and another as an argument")
+        attention_mask = batch.get("attention_mask") if attention_mask is None else attention_mask
+        labels = batch.get("labels") if labels is None else labels
+        batch = batch["input_ids"]
+    elif isinstance(batch, (list, tuple)) and len(batch) == 2 and all(isinstance(t, torch.Tensor) for t in batch):
         if attention_mask is not None:
-            raise TypeError("pretrain_step: an attention mask in the batch and another as an argument")
+            raise TypeError(f"{who}: an attention mask in the batch and another as an argument")
         batch, attention_mask = batch
     elif not isinstance(batch, torch.Tensor):
         strings = True
     ids = _ids_of(batch, dev, _kmer_k(model) if strings else 0)
     if attention_mask is not None:
         attention_mask = attention_mask.to(dev)
-    optimizer.zero_grad()
+    return ids, attention_mask, labels, strings
+
+
+def _sample(model, ids, attention_mask, strings, sampler, mask_ratio, mlm_probability, label_capacity, seed, labels, who: str):
+    """(masked ids, rows, targets, n_valid, attention_mask) of one batch: the fixed-count sampler, BERT's, or the caller's own `labels`"""
+    V = model.bert.embeddings.word_embeddings.weight.shape[0]
+    if labels is not None:
+        if tuple(labels.shape) != tuple(ids.shape):
+            raise ValueError(f"{who}: labels must be [b, S] like the ids")
+        rows, targets, n_valid = ops.mlm_compact_labels(labels.to(device=ids.device, dtype=torch.int64).contiguous(), V, label_capacity,
+                                                        overflow=model.label_overflow)
+        return ids, rows, targets, n_valid, attention_mask
     if sampler == "fixed":
         if label_capacity is not None:
-            raise TypeError('pretrain_step: label_capacity belongs to sampler="bert"')
+            raise TypeError(f'{who}: label_capacity belongs to sampler="bert"')
         masked, rows, targets, n_valid = mask_tokens(ids, mask_ratio, seed)
+        return masked, rows, targets, n_valid, attention_mask
+    if strings and attention_mask is None:
+        attention_mask = barcode_attention_mask(ids)
+    masked, labels = mask_tokens_bert(ids, attention_mask, mlm_probability, seed, vocab_size=model)
+    if label_capacity is None:
+        label_capacity = ops.mlm_label_capacity(ids.numel(), mlm_probability)
+    rows, targets, n_valid = ops.mlm_compact_labels(labels, V, label_capacity, overflow=model.label_overflow)   # keeps the count for the caller
+    return masked, rows, targets, n_valid, attention_mask
+
+
+def _window_of(optimizer, accumulation_steps, world_size, who: str):
+    """(k, exact): k from the argument or the optimizer; exact = the sum-mode window (k > 1 or W > 1), which needs the flat bucket"""
+    have = getattr(optimizer, "accumulation_steps", 1)
+    k = have if accumulation_steps is None else int(accumulation_steps)
+    if k < 1 or int(world_size) < 1:
+        raise ValueError(f"{who}: accumulation_steps and world_size must be >= 1")
+    exact = k > 1 or int(world_size) > 1
+    if exact and not hasattr(optimizer, "divisor_slot"):
+        raise NotSupportedYet(f"{who}: accumulation_steps > 1 or world_size > 1 needs clibd_amd.optim.FusedAdamW / FusedAdam (the flat "
+                              "gradient bucket is the accumulator and the all-reduce message)")
+    if k != have:
+        if getattr(optimizer, "window_open", False):
+            raise ValueError(f"{who}: accumulation_steps={k} in the middle of the optimizer's window of {have}")
+        optimizer.accumulation_steps = k
+    return k, exact
+
+
+def pretrain_step(model: BarcodeBERTForPreTraining, batch, optimizer, mask_ratio: float = 0.5, seed: Optional[int] = None, sampler: str = "fixed",
+                  mlm_probability: float = 0.15, attention_mask: Optional[torch.Tensor] = None, label_capacity: Optional[int] = None,
+                  accumulation_steps: Optional[int] = None, world_size: int = 1, rank: int = 0, labels: Optional[torch.Tensor] = None):
+    """mask -> forward -> backward -> optimizer step on one batch; returns the device tensors (loss, correct, n_valid).  No host
+    synchronisation.
+    batch: token ids int64 [b, S], a pair (ids, attention_mask), a list of barcode strings, or an HF collator's dict ("input_ids", and
+        optionally "attention_mask" and "labels": with labels the ids are used as they are, see labels= below).
+    sampler="fixed" (the default): `mask_tokens` at `mask_ratio`, exactly n_mask rows per sequence; an attention mask, if one is given,
+        reaches the encoder; barcode strings get none (as before).
+    sampler="bert": `mask_tokens_bert` at `mlm_probability` with 80/10/10 replacement and HF-style labels.  Barcode strings get the
+        mask of `barcode_attention_mask` (the trailing <UNK> run of a sequence is padding).  label_capacity=None: ceil(b S min(1, p +
+        6 sqrt(p (1 - p) / (b S)))) rounded up to 64 — six binomial standard deviations over the mean.  Overflow sets
+        `model.label_overflow`; `pretrain_epoch` raises on it.
+    labels= (HF-style int64 [b, S], -100 = ignore): the caller's own collator; the ids are used as they are and no sampler runs
+        (label_capacity=None: b S rounded up).
+    accumulation_steps=k (None: the optimizer's), world_size=W, rank=r: with k > 1 or W > 1 this call is ONE MICRO-STEP of a window of k
+        (the module docstring has the rule).  The loss runs in sum mode: the returned loss is the micro-batch's SUM of row losses, and
+        `optimizer.aux[AUX_COUNT], [AUX_LOSS], [AUX_HITS]` hold the window's totals (all ranks', once the window has closed) until the next
+        window opens.  The closing micro-step issues the one all-reduce (W > 1) and the update; `optimizer.window_closes` tells which.
+        The process group must exist; sharding the data and broadcasting the parameters (`pretrain_epoch` does the latter) are the caller's."""
+    if sampler not in ("fixed", "bert"):
+        raise ValueError('pretrain_step: sampler is "fixed" or "bert"')
+    k, exact = _window_of(optimizer, accumulation_steps, world_size, "pretrain_step")
+    ids, attention_mask, labels, strings = _batch_inputs(model, batch, attention_mask, labels, "pretrain_step")
+    optimizer.zero_grad()
+    if not exact:
+        masked, rows, targets, n_valid, attention_mask = _sample(model, ids, attention_mask, strings, sampler, mask_ratio, mlm_probability,
+                                                                 label_capacity, seed, labels, "pretrain_step")
         loss, correct = model(masked, rows, targets, n_valid, attention_mask=attention_mask)
-    else:
-        if strings and attention_mask is None:
-            attention_mask = barcode_attention_mask(ids)
-        masked, labels = mask_tokens_bert(ids, attention_mask, mlm_probability, seed, vocab_size=model)
-        if label_capacity is None:
-            label_capacity = ops.mlm_label_capacity(ids.numel(), mlm_probability)
-        V = model.bert.embeddings.word_embeddings.weight.shape[0]   # what model(input_ids=, labels=) does, keeping the count for the caller
-        rows, targets, n_valid = ops.mlm_compact_labels(labels, V, label_capacity, overflow=model.label_overflow)
-        loss, correct = model(masked, rows, targets, n_valid, attention_mask=attention_mask)
+        loss.backward()
+        optimizer.step()
+        return loss.detach(), correct, n_valid
+    optimizer.divisor_slot, optimizer.grad_scale = AUX_COUNT, 1.0
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())   # the CPU generator: the same value on equally seeded ranks
+    micro = optimizer.step_count * k + optimizer.micro_steps
+    masked, rows, targets, n_valid, attention_mask = _sample(model, ids, attention_mask, strings, sampler, mask_ratio, mlm_probability,
+                                                             label_capacity, micro_seed(seed, rank, micro), labels, "pretrain_step")
+    with torch.random.fork_rng(devices=[]):   # the tower draws its dropout base from the CPU generator: give it this rank's and micro-step's
+        torch.manual_seed(micro_seed(seed ^ 0x5DEECE66, rank, micro))
+        loss, correct = model(masked, rows, targets, _one(ids.device), attention_mask=attention_mask)   # n_valid = 1: the sum of the row losses
+    optimizer.aux[AUX_COUNT : AUX_HITS + 1].add_(torch.cat([n_valid.to(F32), loss.detach().reshape(1), correct.to(F32)]))
     loss.backward()
+    if optimizer.window_closes and world_size > 1:
+        torch.distributed.all_reduce(optimizer.flat_comm)   # SUM: gradients, count, loss sum and hits in one message, once per window
     optimizer.step()
     return loss.detach(), correct, n_valid
 
 
+def _broadcast_parameters(model, optimizer):
+    """rank 0's parameters to every rank (train.Trainer.__init__'s rule): the trainable values are one message, the rest follow tensor
+    by tensor; `.data` writes do not bump Parameter._version, so the tower's bf16 weight images are dropped explicitly"""
+    import torch.distributed as dist
+
+    dist.broadcast(optimizer.flat_p, src=0)
+    own = {id(p) for p in optimizer.bucket_params()}
+    with torch.no_grad():
+        for t in list(model.parameters()) + list(model.buffers()):
+            if id(t) not in own:
+                dist.broadcast(t.data, src=0)
+    tw = model.tower()
+    if hasattr(tw, "invalidate_weight_images"):
+        tw.invalidate_weight_images()
+
+
 def pretrain_epoch(model: BarcodeBERTForPreTraining, loader, optimizer, scheduler=None, mask_ratio: float = 0.5, log_every: int = 0,
-                   sampler: str = "fixed", mlm_probability: float = 0.15, label_capacity: Optional[int] = None):
+                   sampler: str = "fixed", mlm_probability: float = 0.15, label_capacity: Optional[int] = None,
+                   accumulation_steps: Optional[int] = None, world_size: int = 1, rank: int = 0, seed: Optional[int] = None,
+                   broadcast_parameters: bool = True):
     """One pass over `loader` (int64 [b, S] ids, (ids, attention_mask) pairs or lists of barcode strings) in train mode; `sampler`,
     `mlm_probability` and `label_capacity` as in `pretrain_step`.  `optimizer`: clibd_amd.optim.FusedAdamW over
     model.parameters(), wired to the backward here as simclr.py wires its own; `scheduler` (optional) is stepped per batch.  The loss and
@@ -398,32 +530,107 @@ def pretrain_epoch(model: BarcodeBERTForPreTraining, loader, optimizer, schedule
     steps, a host synchronisation each); the same fetch reads `model.label_overflow` and raises RuntimeError if a step met more labelled
     positions than its capacity, and `optimizer.skipped_steps` (clibd_amd.optim, nonfinite="skip").  Returns {"loss": mean step loss,
     "accuracy": hits / valid targets, "steps": n, "skipped": steps this epoch dropped for a non-finite gradient norm (0 for an optimizer
-    without the counter)}.  A skipped step still counts in "steps" and its loss still enters the mean, so a NaN loss shows there."""
+    without the counter)}.  A skipped step still counts in "steps" and its loss still enters the mean, so a NaN loss shows there.
+
+    accumulation_steps=k (None: the optimizer's), world_size=W, rank=r, seed (None: drawn per micro-step from the CPU generator): with
+    k > 1 or W > 1 every batch of `loader` is a micro-batch (the module docstring has the rule): the scheduler is stepped once per applied
+    window, a partial window at the loader's end is applied (`optimizer.flush()`, after its all-reduce; every rank must see the same
+    number of batches), "loss" is the sum of row losses / the sum of labelled counts over the epoch and over all ranks, "accuracy" likewise,
+    "steps" counts updates, and log_every counts updates too.  W > 1: rank 0's parameters are broadcast first
+    (broadcast_parameters=False when the caller has done it)."""
     if hasattr(optimizer, "flat_g"):
         model.attach(optimizer)
     model.train()
     dev = next(model.parameters()).device
+    k, exact = _window_of(optimizer, accumulation_steps, world_size, "pretrain_epoch")
     acc = torch.zeros((3,), dtype=torch.float64, device=dev)   # sum of step losses, hits, valid targets
     n = 0
     counter = getattr(optimizer, "skipped_steps", None)
     skipped0 = counter.clone() if counter is not None else torch.zeros((1,), dtype=torch.int32, device=dev)   # a device copy, no fetch
-    for batch in loader:
-        loss, correct, n_valid = pretrain_step(model, batch, optimizer, mask_ratio, sampler=sampler, mlm_probability=mlm_probability,
-                                               label_capacity=label_capacity)
-        acc += torch.stack([loss.double(), correct[0].double(), n_valid[0].double()])
-        n += 1
-        if scheduler is not None:
-            scheduler.step()
-        if log_every and n % log_every == 0:
-            s = acc.tolist()
-            print(f"step {n}\tloss {s[0] / n:.4f}\tmasked-token accuracy {s[1] / max(s[2], 1.0):.4f}")
+    if not exact:
+        for batch in loader:
+            loss, correct, n_valid = pretrain_step(model, batch, optimizer, mask_ratio, sampler=sampler, mlm_probability=mlm_probability,
+                                                   label_capacity=label_capacity)
+            acc += torch.stack([loss.double(), correct[0].double(), n_valid[0].double()])
+            n += 1
+            if scheduler is not None:
+                scheduler.step()
+            if log_every and n % log_every == 0:
+                s = acc.tolist()
+                print(f"step {n}\tloss {s[0] / n:.4f}\tmasked-token accuracy {s[1] / max(s[2], 1.0):.4f}")
+    else:
+        if world_size > 1 and broadcast_parameters:
+            _broadcast_parameters(model, optimizer)
+        if optimizer.window_open:
+            raise ValueError("pretrain_epoch: the optimizer is in the middle of a window")
+
+        def applied():   # the window's totals (all ranks') sit in aux until the next zero_grad
+            nonlocal n
+            acc.add_(torch.stack([optimizer.aux[AUX_LOSS].double(), optimizer.aux[AUX_HITS].double(), optimizer.aux[AUX_COUNT].double()]))
+            n += 1
+            if scheduler is not None:
+                scheduler.step()
+            if log_every and n % log_every == 0:
+                s = acc.tolist()
+                print(f"update {n}\tloss {s[0] / max(s[2], 1.0):.4f}\tmasked-token accuracy {s[1] / max(s[2], 1.0):.4f}")
+
+        for batch in loader:
+            pretrain_step(model, batch, optimizer, mask_ratio, seed=seed, sampler=sampler, mlm_probability=mlm_probability,
+                          label_capacity=label_capacity, accumulation_steps=k, world_size=world_size, rank=rank)
+            if not optimizer.window_open:
+                applied()
+        if optimizer.window_open:   # a partial window at the loader's end
+            if world_size > 1:
+                torch.distributed.all_reduce(optimizer.flat_comm)
+            optimizer.flush()
+            applied()
     skipped = (counter if counter is not None else skipped0) - skipped0
     s = torch.cat([acc, model.label_overflow.double(), skipped.double()]).tolist()   # the one host fetch of the epoch
     if s[3] != 0:
         model.label_overflow.zero_()
         raise RuntimeError("pretrain_epoch: a step labelled more positions than its label_capacity (model.label_overflow): rows were left "
                            "out of the loss; rerun with a larger capacity or label_capacity=None")
+    if exact:
+        return {"loss": s[0] / max(s[2], 1.0), "accuracy": s[1] / max(s[2], 1.0), "steps": n, "skipped": int(s[4])}
     return {"loss": s[0] / max(n, 1), "accuracy": s[1] / max(s[2], 1.0), "steps": n, "skipped": int(s[4])}
+
+
+def evaluate(model: BarcodeBERTForPreTraining, loader, sampler: str = "fixed", seed: int = 0, world_size: int = 1, rank: int = 0,
+             mask_ratio: float = 0.5, mlm_probability: float = 0.15, label_capacity: Optional[int] = None):
+    """Score a held-out set: a no-grad, eval-mode pass over `loader` (the batch forms of `pretrain_step`); batch number i of rank r is
+    masked by `sampler` with the seed `micro_seed(seed, r, i)`, so the same seed scores the same masks every time (a dict batch with
+    "labels" is scored on those).  Returns the
+    token-weighted {"loss": sum of row losses / labelled positions, "accuracy": hits / labelled positions, "perplexity": exp(loss),
+    "tokens": labelled positions} over all batches (and all ranks: one all-reduce of the three sums under world_size > 1, each rank scoring
+    its shard).  The sums accumulate on the device in fp64; one host fetch, which also checks `model.label_overflow` (RuntimeError).
+    Parameters, optimizer state and the caller's train / eval mode are left as they were."""
+    import math
+
+    if sampler not in ("fixed", "bert"):
+        raise ValueError('evaluate: sampler is "fixed" or "bert"')
+    was_training = model.training
+    model.eval()
+    dev = next(model.parameters()).device
+    acc = torch.zeros((3,), dtype=torch.float64, device=dev)   # sum of row losses, hits, labelled positions
+    try:
+        with torch.no_grad():
+            for i, batch in enumerate(loader):
+                ids, attention_mask, labels, strings = _batch_inputs(model, batch, None, None, "evaluate")
+                masked, rows, targets, n_valid, attention_mask = _sample(model, ids, attention_mask, strings, sampler, mask_ratio, mlm_probability,
+                                                                         label_capacity, micro_seed(seed, rank, i), labels, "evaluate")
+                loss, correct = model(masked, rows, targets, _one(dev), attention_mask=attention_mask)   # n_valid = 1: the sum
+                acc += torch.stack([loss.double(), correct[0].double(), n_valid[0].double()])
+    finally:
+        model.train(was_training)
+    if world_size > 1:
+        torch.distributed.all_reduce(acc)
+    s = torch.cat([acc, model.label_overflow.double()]).tolist()   # the one host fetch
+    if s[3] != 0:
+        model.label_overflow.zero_()
+        raise RuntimeError("evaluate: a batch labelled more positions than its label_capacity (model.label_overflow)")
+    tokens = max(s[2], 1.0)
+    loss = s[0] / tokens
+    return {"loss": loss, "accuracy": s[1] / tokens, "perplexity": math.exp(loss) if loss < 700 else float("inf"), "tokens": int(s[2])}
 
 
 def bert_config_of(model) -> dict:

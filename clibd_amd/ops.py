@@ -866,6 +866,25 @@ def grad_norm(g: torch.Tensor, record: torch.Tensor, ws: torch.Tensor, grad_scal
                                       int(bool(skip_nonfinite)), record.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "grad_norm")
 
 
+def grad_norm_div(g: torch.Tensor, record: torch.Tensor, ws: torch.Tensor, divisor: Optional[torch.Tensor], grad_scale: float = 1.0,
+                  max_norm: Optional[float] = None, skip_nonfinite: bool = False) -> None:
+    """`grad_norm` with a divisor on the device (include/clibd_hip_accum.h): `divisor` fp32 [1] or None; with d = max(divisor, 1) the record
+    gets total_norm = grad_scale * sqrt(sum g^2) / d and coef = clip(total_norm) / d, so the grouped updates, which multiply the gradient
+    by grad_scale * coef, apply the averaged and clipped gradient of an accumulation window.  None or 1: `grad_norm`'s record bit for bit.
+    The workspace is `grad_norm_workspace`'s."""
+    _chk(g, F32, "g")
+    _chk(record, torch.int32, "record")
+    if g.dim() != 1 or record.numel() != 4:
+        raise ValueError("grad_norm_div: g is flat, record is int32 [4]")
+    if divisor is not None:
+        _chk(divisor, F32, "divisor")
+        if divisor.numel() != 1:
+            raise ValueError("grad_norm_div: divisor is fp32 [1]")
+    check(_lib.load().clibd_grad_norm_div(g.data_ptr(), g.numel(), float(grad_scale), 0.0 if max_norm is None else float(max_norm),
+                                          int(bool(skip_nonfinite)), _p(divisor), record.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "grad_norm_div")
+
+
 def _step_groups(entry, what, p, g, m, v, groups, beta1, beta2, eps, step, grad_scale, record):
     import ctypes
 

@@ -21,8 +21,24 @@ Beyond the plain update (include/clibd_hip_optim.h):
     bucket and takes the same decision, so there is no new collective.
 With no `max_grad_norm`, "propagate" and one group, `step()` is the single launch of `ops.adamw_step` / `ops.adam_l2_step` it always was.
 
+Accumulation windows (include/clibd_hip_accum.h): `accumulation_steps=k`.  The driver goes on calling `zero_grad()` and
+`step()` once per micro-batch: `zero_grad()` clears the bucket (and `aux`) only when a window opens, every backward adds into it, and
+`step()` launches nothing until the k-th call of the window, which applies the window's gradient and advances `step_count` once.
+`window_closes` says whether the next `step()` applies; `flush()` applies a partial window (an epoch's end).  The divisor:
+  - by default the number of micro-steps taken, on the host, folded into `grad_scale`: the mean of the micro-batches' mean gradients, HF
+    Trainer's classic semantics for micro-batches of equal size.  The launches are those of a k = 1 step on the same bucket with
+    grad_scale / micro-steps;
+  - `divisor_slot = i`: `aux[i]` on the device, read by `ops.grad_norm_div` — a count (fp32, exact to 2^24) that the driver summed there and
+    that rode through the all-reduce with the gradients, e.g. the labelled positions of a masked-LM window (clibd_amd.mlm).  The update is
+    then always the norm launch plus the grouped update, whose factor grad_scale * coef carries the division.
+`max_grad_norm` and `nonfinite="skip"` act on the window's averaged gradient; a skipped window leaves p, m and v untouched.
+`checkpoint.save_training_state` refuses in the middle of a window.  A driver that issues the bucket's all-reduce itself, per step
+(`train.Trainer`, `simclr.SimCLR`), raises ValueError for accumulation_steps > 1 under world_size > 1: a bucket reduced twice is silently
+wrong.  Accumulating a contrastive loss is not the loss of the large batch (the negatives of a micro-batch are its own), so the contrastive
+`Trainer` does not use windows.  With accumulation_steps=1 and no divisor slot every launch is what it was.
+
 Refused or not here: norm types other than 2, clipping by value, per-group betas or eps, amsgrad, maximize, more than 8 groups, LAMB and
-LARS, gradient accumulation, a device-side step counter.
+LARS, gradient accumulation of a contrastive loss (gradient accumulation itself: above and §3.18), a device-side step counter.
 """
 from __future__ import annotations
 
@@ -39,8 +55,10 @@ class FusedAdamW(torch.optim.Optimizer):
     AUX_SLOTS = 64  # spare fp32 slots behind the gradients in the same allocation: scalars that ride along the gradient all-reduce
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm: Optional[float] = None,
-                 nonfinite: str = "propagate"):
+                 nonfinite: str = "propagate", accumulation_steps: int = 1):
         name = type(self).__name__
+        if isinstance(accumulation_steps, bool) or not isinstance(accumulation_steps, int) or accumulation_steps < 1:
+            raise ValueError(f"{name}: accumulation_steps must be an integer >= 1")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError(f"{name}: max_grad_norm must be positive (None: no clipping)")
         if nonfinite not in ("propagate", "skip"):
@@ -65,6 +83,9 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError(f"{name}: betas and eps are shared by all parameter groups")
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.nonfinite = nonfinite
+        self.accumulation_steps = accumulation_steps
+        self.divisor_slot = None   # an index into `aux`: the window's divisor is that device value, not the host's micro-step count
+        self._micro = 0            # micro-steps taken in the open window
         ps = self.bucket_params()
         dev = ps[0].device
         self._check_params(ps, dev)
@@ -109,9 +130,25 @@ class FusedAdamW(torch.optim.Optimizer):
         """every parameter in bucket order (group after group): `_offsets[i]` is where `bucket_params()[i]` starts"""
         return [p for g in self.param_groups for p in g["params"]]
 
+    @property
+    def window_closes(self) -> bool:
+        """True iff the next `step()` applies the update (always, with accumulation_steps=1)"""
+        return self._micro + 1 >= self.accumulation_steps
+
+    @property
+    def window_open(self) -> bool:
+        """True between the first `step()` of a window and the one that applies it"""
+        return self._micro > 0
+
+    @property
+    def micro_steps(self) -> int:
+        """micro-steps taken in the open window (0: none is open)"""
+        return self._micro
+
     def zero_grad(self, set_to_none: bool = False):
-        # gradients stay resident as views of the flat bucket (autograd accumulates in place)
-        self.flat_comm.zero_()
+        # gradients stay resident as views of the flat bucket (autograd accumulates in place); inside a window they are kept
+        if self._micro == 0:
+            self.flat_comm.zero_()
         for p, off in zip(self.bucket_params(), self._offsets):
             k = p.numel()
             if p.grad is None or p.grad.data_ptr() != self.flat_g.data_ptr() + 4 * off:
@@ -120,22 +157,43 @@ class FusedAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        self._micro += 1
+        if self._micro >= self.accumulation_steps:
+            self._apply()
+        return loss
+
+    @torch.no_grad()
+    def flush(self) -> bool:
+        """apply the open window although it holds fewer than accumulation_steps micro-steps; False (and no launch) when none is open"""
+        if self._micro == 0:
+            return False
+        self._apply()
+        return True
+
+    def _apply(self):
+        slot = self.divisor_slot
+        if slot is not None and not 0 <= int(slot) < self.AUX_SLOTS:
+            raise ValueError(f"{type(self).__name__}: divisor_slot must be in 0..{self.AUX_SLOTS - 1}")
+        micro, self._micro = self._micro, 0
         g = self.param_groups[0]
         self.step_count += 1
         b1, b2 = g["betas"]
         skip = self.nonfinite == "skip"
-        if self.max_grad_norm is None and not skip and len(self.param_groups) == 1:
+        # the host's divisor: mean of the micro-batches' means.  micro == 1 leaves grad_scale as it is (x / 1), so k = 1 is what it was
+        scale = self.grad_scale if slot is not None or micro == 1 else self.grad_scale / micro
+        if slot is None and self.max_grad_norm is None and not skip and len(self.param_groups) == 1:
             self._update(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, g["lr"], b1, b2, g["eps"], g["weight_decay"],
-                         self.step_count, self.grad_scale)
-            return loss
+                         self.step_count, scale)
+            return
         record = None
-        if self.max_grad_norm is not None or skip:
+        if slot is not None:
             record = self._record
-            ops.grad_norm(self.flat_g, record, self._norm_ws, self.grad_scale, self.max_grad_norm, skip)
+            ops.grad_norm_div(self.flat_g, record, self._norm_ws, self.aux[int(slot) : int(slot) + 1], scale, self.max_grad_norm, skip)
+        elif self.max_grad_norm is not None or skip:
+            record = self._record
+            ops.grad_norm(self.flat_g, record, self._norm_ws, scale, self.max_grad_norm, skip)
         table = [(first, grp["lr"], grp["weight_decay"]) for first, grp in zip(self._group_first, self.param_groups)]
-        self._update_groups(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, table, b1, b2, g["eps"], self.step_count, self.grad_scale,
-                            record)
-        return loss
+        self._update_groups(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, table, b1, b2, g["eps"], self.step_count, scale, record)
 
     def _update(self, *args):
         ops.adamw_step(*args)
@@ -147,17 +205,26 @@ class FusedAdamW(torch.optim.Optimizer):
 class FusedAdam(FusedAdamW):
     """torch.optim.Adam(weight_decay=...) on the same flat bucket: the decay is L2 added to the gradient before the moments, not AdamW's
     decoupled shrink (the SimCLR pre-training's optimizer, reference scripts/unimodel/unimodel_training_for_image_encoder.py).
-    Parameter groups, `max_grad_norm` and `nonfinite` as in FusedAdamW."""
+    Parameter groups, `max_grad_norm`, `nonfinite` and `accumulation_steps` as in FusedAdamW."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm: Optional[float] = None,
-                 nonfinite: str = "propagate"):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, nonfinite=nonfinite)
+                 nonfinite: str = "propagate", accumulation_steps: int = 1):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, nonfinite=nonfinite,
+                         accumulation_steps=accumulation_steps)
 
     def _update(self, *args):
         ops.adam_l2_step(*args)
 
     def _update_groups(self, *args):
         ops.adam_l2_step_groups(*args)
+
+
+def refuse_windows_under_data_parallel(optimizer, who: str) -> None:
+    """for drivers that all-reduce the flat bucket themselves, once per micro-step: with accumulation_steps > 1 the sum of the first
+    micro-steps would be reduced again with every later one"""
+    if getattr(optimizer, "accumulation_steps", 1) > 1:
+        raise ValueError(f"{who}: accumulation_steps > 1 under world_size > 1: this driver all-reduces the gradient bucket at every step, and "
+                         "a bucket reduced twice is silently wrong (clibd_amd.mlm reduces once per window)")
 
 
 def decay_parameter_names(module: torch.nn.Module):

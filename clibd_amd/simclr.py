@@ -157,7 +157,9 @@ class SimCLR(object):
     Arithmetic: bf16 GEMM operands with fp32 accumulation, fp32 statistics, fp32 master weights and optimizer state, where the
     reference runs fp16 autocast with a GradScaler; there is no wandb / tensorboard logging.
     world_size > 1: like the reference, every rank computes the loss over its own 2b rows (no gather) and the gradients are averaged,
-    here through one all-reduce of the optimizer's flat bucket (unmeasured on more than one GPU)."""
+    here through one all-reduce of the optimizer's flat bucket (unmeasured on more than one GPU); that all-reduce runs at every step,
+    so an optimizer with accumulation_steps > 1 raises ValueError there.  On one GPU such an optimizer accumulates the NT-Xent gradients
+    of k steps (mean of means), which is NOT the loss of the k-times larger batch: a micro-batch's negatives are its own."""
 
     def __init__(self, *args, **kwargs):
         self.args = kwargs["args"]
@@ -170,6 +172,9 @@ class SimCLR(object):
         self._dist = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
         if hasattr(self.optimizer, "flat_g"):
             if self._dist:
+                from .optim import refuse_windows_under_data_parallel
+
+                refuse_windows_under_data_parallel(self.optimizer, "SimCLR")
                 self.optimizer.grad_scale = 1.0 / torch.distributed.get_world_size()   # SUM all-reduce, then DDP's mean
             if hasattr(self.model, "tower"):
                 self.model.tower().grad_sink = {id(p): p.grad for p in self.optimizer.bucket_params()}

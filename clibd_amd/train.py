@@ -13,7 +13,7 @@ import torch
 
 from . import augment
 from .model.loss_func import ClipLoss, ContrastiveLoss, collectives_forced
-from .optim import FusedAdamW
+from .optim import FusedAdamW, refuse_windows_under_data_parallel
 
 try:
     import torch.distributed as dist
@@ -85,7 +85,11 @@ class Trainer:
         reductions, a step repeats bit for bit on one GPU; RCCL's all-reduce order across ranks is not covered); None keeps the model's setting.
         max_grad_norm, nonfinite: handed to the FusedAdamW (clibd_amd.optim): global-norm clipping of the all-reduced, averaged gradient and
         the device-side skip of a step whose norm is inf or NaN; `self.optimizer.grad_norm` / `.skipped_steps` are device tensors.  The
-        norm is summed in a fixed order in every mode.  The defaults keep the single plain update launch."""
+        norm is summed in a fixed order in every mode.  The defaults keep the single plain update launch.
+        There is no accumulation_steps here: the contrastive loss of k micro-batches is not the loss of the batch k times the size (a
+        micro-batch's negatives are its own), so accumulating it is not large-batch training (a GradCache-style chunked step would be
+        another feature).  An optimizer with accumulation_steps > 1 put in this Trainer's place raises ValueError in the data-parallel
+        step: the bucket would be all-reduced once per micro-step."""
         self.model, self.world_size, self.rank = model, world_size, rank
         if numerics:    # e.g. dict(residual_grad="fp32"): the reference's fp32 residual-gradient stream (engine.NUMERICS_CHOICES)
             model.set_numerics(**numerics)
@@ -178,6 +182,7 @@ class Trainer:
             self.model.join_streams()  # tower backward passes ran on the towers' own streams
         loss = loss.detach()
         if self._dist:
+            refuse_windows_under_data_parallel(self.optimizer, "Trainer")   # an optimizer swapped in with accumulation_steps > 1
             fold = not getattr(self.criterion, "reduce_loss_value", True)
             if fold:
                 self.optimizer.aux[0:1].copy_(loss.reshape(1))     # partial sums add up to the full-batch loss
