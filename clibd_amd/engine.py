@@ -222,6 +222,10 @@ class TransformerStack:
         self.deterministic = default_deterministic()   # fixed-order reductions in the backward (see default_deterministic)
         self._c2, self._c2_age = None, 0   # dgrad = "fp8" under full fine-tune: the per-layer d(fc1 out) scales and how many refreshes old they are
         self.dgrad8_sites = ("mlp", "proj")   # dgrad = "fp8": which of the covered GEMMs take it ("mlp" = the fc2 -> fc1 pair, "proj"); tools/dgrad8_sites_study.py
+        # True: a forward that saves nothing still runs the TRAINING forward's arithmetic — fc1 applies GELU to the bf16-rounded pre-activation
+        # and writes gelu' (into a scratch buffer), where the plain no-grad forward takes the fp32 pre-activation.  The chunked step's first
+        # pass sets it (clibd_amd.chunked): its cached embeddings must be the bits the saving forward of pass 2 produces.
+        self.train_arithmetic = False
 
     HEAD_DIMS = (64, 128, 192)
     DGRAD8_C2_EVERY = 64  # full fine-tune: refreshes (= steps) between two host reads of the fc2 images' l1 norms
@@ -486,6 +490,8 @@ class TransformerStack:
             w1, b1, act, pre = c.w1g, c.b1f, ops.ACT_GELU_SAVE_GRAD, h if h is not None else p.h_tmp
             kw = dict(row_stats=fold_st, col_sum_w=c.s1)
         else:
+            if h is None and p.scratch_h is not None:
+                h = p.new(*p.scratch_h, x.shape[0])   # train_arithmetic: gelu' goes to a scratch buffer nobody reads
             w1, b1, act, pre, kw = c.w1, c.b1, p.act_save if h is not None else ops.ACT_GELU, h, {}
         ops.gemm_nt(x, w1, bias=b1, act=act, out_pre=pre, out_bf16=a, **kw)
         ops.gemm_nt(a, c.w2, bias=c.b2, residual=res, out_f32=out, drop=drop)
@@ -543,7 +549,7 @@ class TransformerStack:
         if fold and h_tmp is None and not save:
             h_tmp = new(FF, BF16)   # the consumer epilogue always writes gelu' (eval forward: into a scratch buffer)
         p = SimpleNamespace(B=B, S=S, dev=dev, new=new, key_mask=key_mask, keep=keep, sp_ok=sp_ok, act_save=act_save, h_tmp=h_tmp,
-                            fold_sums=fold_sums, save=save)
+                            fold_sums=fold_sums, save=save, scratch_h=(HC, GG) if (self.train_arithmetic and not save) else None)
         t, saved = t0, []
         for i, (L, c) in enumerate(zip(self.layers, self._cache)):
             lora = L.lora is not None

@@ -35,10 +35,12 @@ Accumulation windows (include/clibd_hip_accum.h): `accumulation_s
 `checkpoint.save_training_state` refuses in the middle of a window.  A driver that issues the bucket's all-reduce itself, per step
 (`train.Trainer`, `simclr.SimCLR`), raises ValueError for accumulation_steps > 1 under world_size > 1: a bucket reduced twice is silently
 wrong.  Accumulating a contrastive loss is not the loss of the large batch (the negatives of a micro-batch are its own), so the contrastive
-`Trainer` does not use windows.  With accumulation_steps=1 and no divisor slot every launch is what it was.
+`Trainer` does not use windows: its large-batch form is the chunked step, `Trainer(chunk_size=...)` / `SimCLR(chunk_size=...)` (clibd_amd.chunked,
+DESIGN §3.19).  With accumulation_steps=1 and no divisor slot every launch is what it was.
 
 Refused or not here: norm types other than 2, clipping by value, per-group betas or eps, amsgrad, maximize, more than 8 groups, LAMB and
-LARS, gradient accumulation of a contrastive loss (gradient accumulation itself: above and §3.18), a device-side step counter.
+LARS, gradient accumulation of a contrastive loss (gradient accumulation itself: above and §3.18; the contrastive large batch: the chunked step,
+§3.19), a device-side step counter.
 """
 from __future__ import annotations
 

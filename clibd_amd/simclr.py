@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, simclr_views
+from .chunked import ReplayGuard, two_pass, validate_chunk_size
 from .engine import NotSupportedYet
 from .model.image_encoder import create_vit
 from .model.simple_clip import SimpleCLIP, _get
@@ -159,9 +160,14 @@ class SimCLR(object):
     world_size > 1: like the reference, every rank computes the loss over its own 2b rows (no gather) and the gradients are averaged,
     here through one all-reduce of the optimizer's flat bucket (unmeasured on more than one GPU); that all-reduce runs at every step,
     so an optimizer with accumulation_steps > 1 raises ValueError there.  On one GPU such an optimizer accumulates the NT-Xent gradients
-    of k steps (mean of means), which is NOT the loss of the k-times larger batch: a micro-batch's negatives are its own."""
+    of k steps (mean of means), which is NOT the loss of the k-times larger batch: a micro-batch's negatives are its own.
+    chunk_size=c (keyword, default None = the plain step): `train_step` takes the two-pass chunked step of clibd_amd.chunked
+    over row ranges of c of the 2b views — one NTXentLoss over all 2b rows, `last_top1` of the full batch, the exact gradient of the plain
+    step with the activations of c rows in memory.  `replay_mismatch` is the replay guard's device counter (replay_guard=False: none)."""
 
     def __init__(self, *args, **kwargs):
+        self.chunk_size = validate_chunk_size(kwargs.get("chunk_size"), "SimCLR")
+        self._want_guard, self._guard = bool(kwargs.get("replay_guard", True)) and self.chunk_size is not None, None
         self.args = kwargs["args"]
         self.device = kwargs["device"]
         self.model = kwargs["model"].to(self.device)
@@ -181,6 +187,11 @@ class SimCLR(object):
         elif self._dist:
             raise NotSupportedYet("SimCLR: data-parallel training needs clibd_amd.optim.FusedAdam (the flat gradient bucket is the all-reduce message)")
 
+    @property
+    def replay_mismatch(self):
+        """device int64 [1]: cached feature words the chunked steps' second pass did not reproduce (None without the guard)"""
+        return None if self._guard is None else self._guard.mismatch
+
     def info_nce_loss(self, features):
         """Kept for callers of the reference's method, but returns the LOSS: the reference's (logits, labels) pair — the [2b, 2b-1]
         matrix with the positive moved to column 0 — is never formed.  `self.criterion.last_top1` holds the top-1 hit count."""
@@ -197,9 +208,16 @@ class SimCLR(object):
         else:
             images = torch.cat([images_1, images_2], dim=0).to(self.device)
         self.optimizer.zero_grad()
-        features = self.model(images)
-        loss = self.info_nce_loss(features)
-        loss.backward()
+        if self.chunk_size is not None:
+            if self._guard is None and self._want_guard:
+                self._guard = ReplayGuard(images.device)
+            towers = [self.model.tower()] if hasattr(self.model, "tower") else []
+            loss, _ = two_pass(lambda x: (self.model(x),), (images,), self.chunk_size, lambda leaves: self.info_nce_loss(leaves[0]),
+                               towers=towers, guard=self._guard)
+        else:
+            features = self.model(images)
+            loss = self.info_nce_loss(features)
+            loss.backward()
         if self._dist:
             torch.distributed.all_reduce(self.optimizer.flat_comm)
         self.optimizer.step()

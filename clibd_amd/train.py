@@ -12,6 +12,7 @@ from typing import Optional
 import torch
 
 from . import augment
+from .chunked import ReplayGuard, two_pass, validate_chunk_size
 from .model.loss_func import ClipLoss, ContrastiveLoss, collectives_forced
 from .optim import FusedAdamW, refuse_windows_under_data_parallel
 
@@ -72,7 +73,7 @@ class Trainer:
                  fix_temperature: Optional[float] = None, bind_to=None, no_image_text_loss=False, weight_decay: float = 1e-2,
                  broadcast_parameters: bool = True, bucket_bytes: int = 64 << 20, fp8_recalibrate_every: int = 0,
                  numerics: Optional[dict] = None, deterministic: Optional[bool] = None, max_grad_norm: Optional[float] = None,
-                 nonfinite: str = "propagate"):
+                 nonfinite: str = "propagate", chunk_size: Optional[int] = None, replay_guard: bool = True):
         """bucket_bytes: at world_size > 1, when the gradients are at least two buckets long (full fine-tune: 694 MB), the
         all-reduce is issued in pieces of about this size as the backward completes them, each on the stream that produced
         it, so RCCL runs under the rest of the backward; smaller gradient sets (LoRA: 6 MB) keep the single all-reduce.
@@ -87,10 +88,25 @@ class Trainer:
         the device-side skip of a step whose norm is inf or NaN; `self.optimizer.grad_norm` / `.skipped_steps` are device tensors.  The
         norm is summed in a fixed order in every mode.  The defaults keep the single plain update launch.
         There is no accumulation_steps here: the contrastive loss of k micro-batches is not the loss of the batch k times the size (a
-        micro-batch's negatives are its own), so accumulating it is not large-batch training (a GradCache-style chunked step would be
-        another feature).  An optimizer with accumulation_steps > 1 put in this Trainer's place raises ValueError in the data-parallel
-        step: the bucket would be all-reduced once per micro-step."""
+        micro-batch's negatives are its own), so accumulating it is not large-batch training; the chunked step below is (DESIGN
+        §3.19).  An optimizer with accumulation_steps > 1 put in this Trainer's place raises ValueError in the data-parallel
+        step: the bucket would be all-reduced once per micro-step.
+        chunk_size: None keeps the plain step, launch for launch.  An integer >= 1 takes the two-pass chunked step (clibd_amd.chunked, DESIGN
+        §3.19) over chunks of that many samples of the local batch (a shorter last chunk; one chunk when chunk_size >= b): the exact
+        full-batch contrastive gradient with one chunk's activations in memory, for one extra no-grad forward (measured 1.50 - 1.56 x the plain
+        step's time at b = 2048, a quarter of its peak memory at chunk_size=512).  Still one loss over all
+        rows, one all-gather, one reduce-scatter, one gradient all-reduce (the bucketed pieces go out during the last chunk's backward) and one
+        optimizer update per step.  Dropout masks differ from the plain step's (a fresh base per chunk, chunk-local rows).  Together with
+        fp8_recalibrate_every > 0 it raises ValueError: the calibration forward takes the whole batch.
+        replay_guard (chunked step only): `self.replay_mismatch`, a device int64 [1], counts the cached embedding words pass 2 failed to
+        reproduce bit for bit (0 when the step is sound); a few small launches per chunk, no host synchronisation."""
+        self.chunk_size = validate_chunk_size(chunk_size, "Trainer")
+        if self.chunk_size is not None and int(fp8_recalibrate_every) > 0:
+            raise ValueError("Trainer: chunk_size together with fp8_recalibrate_every > 0: the calibration forward takes the whole batch "
+                             "(calibrate once with SimpleCLIP.enable_fp8_forward(calibration_inputs=...) before training instead)")
         self.model, self.world_size, self.rank = model, world_size, rank
+        self._want_guard, self._guard = bool(replay_guard) and self.chunk_size is not None, None
+        self.cached_embeddings = None   # chunked step: [image, dna, text] fp32 [b, D] (None for an absent tower), what the last loss was taken on
         if numerics:    # e.g. dict(residual_grad="fp32"): the reference's fp32 residual-gradient stream (engine.NUMERICS_CHOICES)
             model.set_numerics(**numerics)
         if deterministic is not None:
@@ -165,6 +181,30 @@ class Trainer:
             self._issue(self._done[ti], upto)
             self._done[ti] = upto
 
+    @property
+    def replay_mismatch(self) -> Optional[torch.Tensor]:
+        """device int64 [1]: cached embedding words the chunked steps' second pass did not reproduce (None without the guard)"""
+        return None if self._guard is None else self._guard.mismatch
+
+    def _chunked_forward_backward(self, image, dna, text, labels) -> torch.Tensor:
+        """the two-pass chunked step up to the point where the plain step has called loss.backward() and joined the streams: the whole
+        batch's gradient sits in the bucket (the temperature's included, written once at the root), the detached loss is returned"""
+        model = self.model
+        if self._guard is None and self._want_guard:
+            self._guard = ReplayGuard(self.optimizer.flat_p.device)
+
+        def forward(image_c, dna_c, text_c):
+            return model(image_c, dna_c, text_c)[:3]
+
+        def root_loss(leaves):
+            logit_scale = model.logit_scale.exp() if self.fix_temperature is None else 1.0 / 0.07
+            return self.criterion(leaves[0], leaves[1], leaves[2], labels, logit_scale)
+
+        sides = lambda: [st for pair in model.__dict__.get("_streams", {}).values() for st in pair]
+        loss, self.cached_embeddings = two_pass(forward, (image, dna, text), self.chunk_size, root_loss, towers=_towers(model), side_streams=sides,
+                                                join=getattr(model, "join_streams", None), guard=self._guard)
+        return loss
+
     def step(self, image, dna, text, labels) -> torch.Tensor:
         """forward (all towers) -> loss -> backward -> gradient all-reduce -> AdamW.  Returns the (device) loss.
         Collectives per step at world_size > 1: one packed all-gather (embeddings + labels), one reduce-scatter (feature
@@ -173,14 +213,17 @@ class Trainer:
             self.model.enable_fp8_forward(calibration_inputs=(image, dna, text))
         self._steps_done += 1
         self.optimizer.zero_grad()
-        image_out, dna_out, text_out, logit_scale, _ = self.model(image, dna, text)
-        if self.fix_temperature is not None:
-            logit_scale = 1.0 / 0.07
-        loss = self.criterion(image_out, dna_out, text_out, labels, logit_scale)
-        loss.backward()
-        if hasattr(self.model, "join_streams"):
-            self.model.join_streams()  # tower backward passes ran on the towers' own streams
-        loss = loss.detach()
+        if self.chunk_size is not None:
+            loss = self._chunked_forward_backward(image, dna, text, labels)
+        else:
+            image_out, dna_out, text_out, logit_scale, _ = self.model(image, dna, text)
+            if self.fix_temperature is not None:
+                logit_scale = 1.0 / 0.07
+            loss = self.criterion(image_out, dna_out, text_out, labels, logit_scale)
+            loss.backward()
+            if hasattr(self.model, "join_streams"):
+                self.model.join_streams()  # tower backward passes ran on the towers' own streams
+            loss = loss.detach()
         if self._dist:
             refuse_windows_under_data_parallel(self.optimizer, "Trainer")   # an optimizer swapped in with accumulation_steps > 1
             fold = not getattr(self.criterion, "reduce_loss_value", True)
