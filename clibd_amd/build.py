@@ -25,9 +25,7 @@ SOURCES = ["capi", "gemm", "gemm256", "gemm256_tn", "layernorm", "attention", "a
 
 
 def _public_headers() -> list[Path]:
-    """the C-ABI headers: clibd_hip.h and the additive ones beside it (clibd_hip_simclr.h, clibd_hip_views.h, clibd_hip_classifier.h,
-    clibd_hip_analysis.h, clibd_hip_rollout.h, clibd_hip_insect.h, clibd_hip_mlp.h, clibd_hip_attn_wide.h, clibd_hip_mlm.h, clibd_hip_jpeg.h,
-    clibd_hip_mlm_labels.h, clibd_hip_optim.h, clibd_hip_accum.h)"""
+    """the C-ABI headers: clibd_hip.h and every additive clibd_hip_*.h beside it (the keys of clibd_amd._lib.HEADERS)"""
     return sorted(INCLUDE.glob("clibd_hip*.h"))
 
 
@@ -60,10 +58,16 @@ def _stale(target: Path, srcs: list[Path]) -> bool:
     return any(s.stat().st_mtime > t for s in srcs)
 
 
+def _code_flags() -> list[str]:
+    """the flags every device compilation shares: the build (_flags) and the resource report (resource_usage)"""
+    return [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-Wno-unused-value"]
+
+
 def _flags(name: str) -> list[str]:
     """Every flag that changes the generated code of unit `name` (hashed into its stamp: ADVICE r4 — a changed --offload-arch or
     optimisation flag must not leave old objects 'current')."""
-    f = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
+    f = _code_flags()
+    f.insert(3, "-fPIC")   # where it has always stood: hipcc hashes the command line into each unit's id, so the order is part of the object's bytes
     if name == "capi":
         f.append(f'-DCLIBD_CSRC_HASH="{csrc_hash()}"')   # clibd_build_hash(): checked by _lib.load() against the sources
     if os.environ.get("CLIBD_GEMM_DIAG") == "1":
@@ -100,28 +104,42 @@ def _compile_one(name: str, report: bool) -> tuple[str, str]:
     return name, r.stderr
 
 
-def _summarise(stderr: str) -> list[str]:
-    rows, cur = [], {}
+_REMARKS = {"VGPRs": "vgpr", "AGPRs": "agpr", "VGPRs Spill": "spill", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occ",
+            "LDS Size [bytes/block]": "lds"}
+
+
+def parse_resource_remarks(stderr: str) -> list[dict]:
+    """hipcc's -Rpass-analysis=kernel-resource-usage remarks as one record per kernel, in the order compiled: `name` (mangled) and the integers
+    `vgpr`, `agpr`, `spill` (VGPRs), `scratch` (bytes per lane), `occ` (waves per SIMD), `lds` (bytes per block)."""
+    rows = []
     for line in stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]):\s*(\S+)", line)
+        m = re.search(r"remark:\s+(Function Name|" + "|".join(map(re.escape, _REMARKS)) + r"):\s*(\S+)", line)
         if not m:
             continue
-        k, v = m.group(1), m.group(2)
-        if k == "Function Name":
-            if cur:
-                rows.append(cur)
-            cur = {"name": v}
-        else:
-            cur[k] = v
-    if cur:
-        rows.append(cur)
-    out = []
-    for r in rows:
-        out.append(
-            f"{r['name'][:70]:70s} vgpr={r.get('VGPRs','?'):>4} agpr={r.get('AGPRs','?'):>3} spill={r.get('VGPRs Spill','?'):>3} "
-            f"scratch={r.get('ScratchSize [bytes/lane]','?'):>4} occ={r.get('Occupancy [waves/SIMD]','?')} lds={r.get('LDS Size [bytes/block]','?')}"
-        )
-    return out
+        if m.group(1) == "Function Name":
+            rows.append({"name": m.group(2)})
+        elif rows:
+            rows[-1][_REMARKS[m.group(1)]] = int(m.group(2))
+    return rows
+
+
+def resource_usage(unit: str) -> list[dict]:
+    """The per-kernel records of csrc/<unit>.hip, compiled device-only to the null device with the build's own code flags."""
+    cmd = [_hipcc()] + _code_flags() + ["--cuda-device-only", "-c", str(CSRC / f"{unit}.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    if r.returncode != 0:
+        raise RuntimeError(f"hipcc failed for {unit}.hip:\n{r.stderr[-2000:]}")
+    return parse_resource_remarks(r.stderr)
+
+
+def report_lines(rows: list[dict]) -> list[str]:
+    """the lines --report prints, one per record"""
+    return [f"{r['name'][:70]:70s} vgpr={r.get('vgpr', '?'):>4} agpr={r.get('agpr', '?'):>3} spill={r.get('spill', '?'):>3} "
+            f"scratch={r.get('scratch', '?'):>4} occ={r.get('occ', '?')} lds={r.get('lds', '?')}" for r in rows]
+
+
+def _summarise(stderr: str) -> list[str]:
+    return report_lines(parse_resource_remarks(stderr))
 
 
 def _unit_hash(name: str) -> str:

@@ -8,7 +8,7 @@
  * conventions (extern "C", caller-owned device buffers and workspaces, `void* stream`, 0 / negative CLIBD_E* status, clibd_last_error for
  * the message, nothing allocates or synchronises, arguments validated on the host before any launch).  The addition is purely additive —
  * no entry of the other four headers changes its signature or its arithmetic — so the ABI version stays 7.  The Python binding keeps
- * these symbols in a fifth table (clibd_amd._lib.ANALYSIS_SIGNATURES).
+ * these symbols under this header's name in clibd_amd._lib.HEADERS.
  *
  * Run offsets (`seg`) are given twice: a device copy that the kernels read and a host copy (`seg_host`, the same C + 1 values) that the
  * entry validates before it launches anything.  No float atomics: every sum has one fixed order, so results repeat bit for bit.

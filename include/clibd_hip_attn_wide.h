@@ -5,7 +5,7 @@
  * A ninth header beside clibd_hip.h and the other additive ones: the same library, the same conventions (extern "C", caller-owned device
  * buffers, `void* stream`, 0 / negative CLIBD_E* status, clibd_last_error for the message, nothing allocates or synchronises, arguments
  * validated on the host before any launch).  The addition is purely additive — no entry of the other headers changes — so the ABI
- * version stays 7.  The Python binding keeps these symbols in a ninth table (clibd_amd._lib.ATTN_WIDE_SIGNATURES).
+ * version stays 7.  The Python binding keeps these symbols under this header's name in clibd_amd._lib.HEADERS.
  *
  * No atomics: the workgroup that owns a (sequence, head) writes its own columns, so two runs agree bit for bit.
  */

@@ -6,8 +6,8 @@
  * A fourth header beside clibd_hip.h, clibd_hip_simclr.h and clibd_hip_views.h: the same library, the same conventions (extern "C",
  * caller-owned device buffers and workspaces, `void* stream`, 0 / negative CLIBD_E* status, clibd_last_error for the message, nothing
  * allocates or synchronises, arguments validated on the host before any launch).  The addition is purely additive — no entry of the
- * other three headers changes its signature or its arithmetic — so the ABI version stays 7.  The Python binding keeps these symbols in a
- * fourth table (clibd_amd._lib.CLS_SIGNATURES).
+ * other three headers changes its signature or its arithmetic — so the ABI version stays 7.  The Python binding keeps these symbols under this
+ * header's name in clibd_amd._lib.HEADERS.
  *
  * No float atomics: every output element and every sum has one fixed order, so results repeat bit for bit.
  */

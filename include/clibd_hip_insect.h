@@ -8,7 +8,7 @@
  * clibd_hip_rollout.h: the same library, the same conventions (extern "C", caller-owned device buffers and workspaces, `void* stream`,
  * 0 / negative CLIBD_E* status, clibd_last_error for the message, nothing allocates or synchronises, arguments validated on the host
  * before any launch).  The addition is purely additive — no entry of the other six headers changes — so the ABI version stays 7.  The
- * Python binding keeps these symbols in a seventh table (clibd_amd._lib.INSECT_SIGNATURES).
+ * Python binding keeps these symbols under this header's name in clibd_amd._lib.HEADERS.
  *
  * No float atomics: every output has one summation order, so two runs agree bit for bit and the result does not depend on the launch
  * shape.

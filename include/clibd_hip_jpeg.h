@@ -7,8 +7,8 @@
  * An eleventh header beside clibd_hip.h and the nine additive ones: the same library, the same conventions (extern "C", caller-owned
  * buffers, `void* stream`, 0 / negative CLIBD_E* status, clibd_last_error for the message prefixed by the entry's name, nothing allocates
  * or synchronises, arguments validated on the host before any launch).  The addition is purely additive — no entry of the other headers
- * changes its signature or its arithmetic — so the ABI version stays 7.  The Python binding keeps these symbols in an eleventh table
- * (clibd_amd._lib.JPEG_SIGNATURES).
+ * changes its signature or its arithmetic — so the ABI version stays 7.  The Python binding keeps these symbols under this
+ * header's name in clibd_amd._lib.HEADERS.
  *
  * No atomics: every output byte has one writer, so two runs agree bit for bit.
  */

@@ -6,8 +6,8 @@
  * A twelfth header beside clibd_hip.h and the ten additive ones: the same library, the same conventions (extern "C", caller-owned device
  * buffers, `void* stream`, 0 / negative CLIBD_E* status, clibd_last_error for the message prefixed by the entry's name, nothing allocates
  * or synchronises, arguments validated on the host before any launch).  The addition is purely additive — no entry of the other headers
- * changes its signature or its arithmetic — so the ABI version stays 7.  The Python binding keeps these symbols in a twelfth table
- * (clibd_amd._lib.MLM_LABELS_SIGNATURES).
+ * changes its signature or its arithmetic — so the ABI version stays 7.  The Python binding keeps these symbols under this
+ * header's name in clibd_amd._lib.HEADERS.
  *
  * No float arithmetic at all: counts, prefix sums and hashes are integers, every output element has one writer, and the only atomics OR
  * a flag bit, so two runs agree bit for bit.

@@ -6,7 +6,7 @@
  * An eighth header beside clibd_hip.h and the six additive ones: the same library, the same conventions (extern "C", caller-owned device
  * buffers, `void* stream`, 0 / negative CLIBD_E* status, clibd_last_error for the message, nothing allocates or synchronises, arguments
  * validated on the host before any launch).  The addition is purely additive — no entry of the other headers changes its signature or
- * its arithmetic — so the ABI version stays 7.  The Python binding keeps these symbols in an eighth table (clibd_amd._lib.MLP_SIGNATURES).
+ * its arithmetic — so the ABI version stays 7.  The Python binding keeps these symbols under this header's name in clibd_amd._lib.HEADERS.
  *
  * Arithmetic.  Every operand is fp32 in memory.  A workgroup splits the tiles it loads on their way into LDS, v = hi + lo with
  * hi = bf16(v), lo = bf16(v - hi), and accumulates hi·hi + hi·lo + lo·hi on the bf16 MFMA in fp32 (relative error ~2^-16, the

@@ -6,8 +6,8 @@
  * A thirteenth header beside clibd_hip.h and the eleven additive ones: the same library, the same conventions (extern "C", caller-owned
  * device buffers, `void* stream`, 0 / negative CLIBD_E* status, clibd_last_error for the message prefixed by the entry's name, nothing
  * allocates or synchronises, arguments validated on the host before any launch).  The addition is purely additive — clibd_adamw_step and
- * clibd_adam_l2_step keep their signatures and their arithmetic — so the ABI version stays 7.  The Python binding keeps these symbols in a
- * thirteenth table (clibd_amd._lib.OPTIM_SIGNATURES).
+ * clibd_adam_l2_step keep their signatures and their arithmetic — so the ABI version stays 7.  The Python binding keeps these symbols under this
+ * header's name in clibd_amd._lib.HEADERS.
  *
  * There is no float atomic anywhere here: two runs on any box agree bit for bit, and deterministic mode needs no second form.
  *

@@ -8,7 +8,7 @@
  * library, the same conventions (extern "C", caller-owned device buffers and workspaces, `void* stream`, 0 / negative CLIBD_E* status,
  * clibd_last_error for the message, nothing allocates or synchronises, arguments validated on the host before any launch).  The addition
  * is purely additive — no entry of the other five headers changes — so the ABI version stays 7.  The Python binding keeps these symbols
- * in a sixth table (clibd_amd._lib.ROLLOUT_SIGNATURES).
+ * under this header's name in clibd_amd._lib.HEADERS.
  *
  * No float atomics: every output has one summation order, so two runs agree bit for bit.  A batch is B independent maps.
  */

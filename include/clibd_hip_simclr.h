@@ -6,7 +6,7 @@
  * A second header beside clibd_hip.h: the same library, the same conventions (extern "C", caller-owned device buffers,
  * `void* stream`, 0 / negative CLIBD_E* status, clibd_last_error for the message, shapes validated on the host before
  * any launch).  The addition is purely additive — no entry of clibd_hip.h changes its signature or its arithmetic — so
- * the ABI version stays 7.  The Python binding keeps these symbols in a second table (clibd_amd._lib.EXT_SIGNATURES).
+ * the ABI version stays 7.  The Python binding keeps these symbols under this header's name in clibd_amd._lib.HEADERS.
  */
 #ifndef CLIBD_HIP_SIMCLR_H
 #define CLIBD_HIP_SIMCLR_H

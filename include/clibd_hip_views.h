@@ -7,7 +7,7 @@
  * A third header beside clibd_hip.h and clibd_hip_simclr.h: the same library, the same conventions (extern "C", caller-owned device
  * buffers, `void* stream`, 0 / negative CLIBD_E* status, clibd_last_error for the message, arguments validated on the host before any
  * launch).  The addition is purely additive — no entry of the other two headers changes its signature or its arithmetic — so the ABI
- * version stays 7.  The Python binding keeps these symbols in a third table (clibd_amd._lib.VIEW_SIGNATURES).
+ * version stays 7.  The Python binding keeps these symbols under this header's name in clibd_amd._lib.HEADERS.
  */
 #ifndef CLIBD_HIP_VIEWS_H
 #define CLIBD_HIP_VIEWS_H

@@ -1,19 +1,23 @@
-"""CPU checks of the drop-in boundary: the C-ABI library builds, loads, and exports exactly what
-include/clibd_hip.h declares (no compute calls here: there is no GPU on the authoring box)."""
+"""CPU checks of the drop-in boundary: the C-ABI library builds, loads, and exports exactly what the headers under include/ declare, with
+the types they declare (no compute calls here: there is no GPU on the authoring box)."""
 import ctypes
-import os
 import re
 from pathlib import Path
 
 import pytest
 
+from tests import header_reference as HR
+
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = ROOT / "include" / "clibd_hip.h"
+# how many functions each header declares: a new header adds its key to clibd_amd._lib.HEADERS and its count here, and needs no test of its own
+SYMBOL_COUNTS = {"clibd_hip.h": 74, "clibd_hip_accum.h": 2, "clibd_hip_analysis.h": 4, "clibd_hip_attn_wide.h": 2, "clibd_hip_classifier.h": 7,
+                 "clibd_hip_insect.h": 3, "clibd_hip_jpeg.h": 3, "clibd_hip_mlm.h": 4, "clibd_hip_mlm_labels.h": 3, "clibd_hip_mlp.h": 3,
+                 "clibd_hip_optim.h": 4, "clibd_hip_rollout.h": 4, "clibd_hip_simclr.h": 4, "clibd_hip_views.h": 2}
 
 
 def declared_symbols():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    return sorted(set(re.findall(r"\b(clibd_[a-z0-9_]+)\s*\(", text)))
+    return HR.mentioned_symbols(HEADER)
 
 
 @pytest.fixture(scope="module")
@@ -38,8 +42,56 @@ def test_library_exports_every_declared_symbol(lib):
 def test_python_binding_covers_every_declared_symbol(lib):
     from clibd_amd import _lib
 
-    assert sorted(_lib.SIGNATURES) == declared_symbols() and len(_lib.SIGNATURES) == 74
+    assert sorted(_lib.HEADERS["clibd_hip.h"]) == declared_symbols() and len(_lib.HEADERS["clibd_hip.h"]) == 74
     assert _lib.load().clibd_abi_version() == _lib.ABI_VERSION == 7
+
+
+@pytest.mark.parametrize("header", HR.headers(), ids=lambda h: h.name)
+def test_header_and_binding_agree_by_type(lib, header):
+    """Every prototype of every header against clibd_amd._lib.HEADERS: the names, the return type, the number of arguments and each
+    argument's type as read from the header's text (tests/header_reference.py), and the loaded function carries them."""
+    from clibd_amd import _lib
+
+    protos, table = HR.prototypes(header), _lib.HEADERS[header.name]
+    assert sorted(protos) == HR.mentioned_symbols(header)       # a `clibd_*(` the prototype reader did not take for a prototype
+    assert sorted(protos) == sorted(table)
+    assert len(protos) == SYMBOL_COUNTS[header.name]
+    assert not [s for s in protos if not hasattr(lib, s)]
+    L = _lib.load()
+    for name, (res, args) in protos.items():
+        assert table[name][0] is res, f"{name}: {header.name} returns {res.__name__}, the binding {table[name][0].__name__}"
+        assert [a.__name__ for a in table[name][1]] == [a.__name__ for a in args], f"{name}: argument types differ from {header.name}"
+        assert table[name][1] == args, name
+        fn = getattr(L, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+
+
+def test_one_table_covers_the_headers_on_disk():
+    from clibd_amd import _lib
+
+    assert set(_lib.HEADERS) == {h.name for h in HR.headers()} == set(SYMBOL_COUNTS)
+    assert len(_lib.SIGNATURES) == 119 == sum(SYMBOL_COUNTS.values())       # no symbol sits under two headers
+    assert _lib.SIGNATURES == {s: sig for table in _lib.HEADERS.values() for s, sig in table.items()}
+    with pytest.raises(ValueError, match="two headers"):
+        _lib._flatten({"a.h": {"clibd_x": (ctypes.c_int, [])}, "b.h": {"clibd_x": (ctypes.c_int, [])}})
+    assert _lib.load().clibd_abi_version() == _lib.ABI_VERSION == 7
+
+
+@pytest.mark.parametrize("header", HR.headers(), ids=lambda h: h.name)
+def test_source_hash_covers_every_header(header, monkeypatch, tmp_path):
+    """csrc_hash() — what clibd_build_hash() bakes in and load() compares — moves with the text of each public header, and every unit depends on it."""
+    from clibd_amd import build
+
+    before = build.csrc_hash()
+    inc = tmp_path / "include"
+    inc.mkdir()
+    for h in HR.headers():
+        (inc / h.name).write_text(h.read_text() + ("\n/* changed */\n" if h == header else ""))
+    monkeypatch.setattr(build, "INCLUDE", inc)
+    assert build.csrc_hash() != before
+    assert inc / header.name in build._deps()
+    monkeypatch.undo()
+    assert build.csrc_hash() == before and header in build._deps()
 
 
 def test_binding_refuses_a_library_built_from_other_sources(lib, monkeypatch):
@@ -54,13 +106,13 @@ def test_binding_refuses_a_library_built_from_other_sources(lib, monkeypatch):
 
 
 def test_epilogue_struct_layout_matches_header():
-    from clibd_amd._lib import GemmEpilogue
+    from clibd_amd._lib import GemmEpilogue, OptimGroup
 
     # 8 pointers + 8 int32 + 4 dropout words + (ABI 3) the three LN-fold pointers: 8*8 + 12*4 + 3*8 = 136 bytes
     assert ctypes.sizeof(GemmEpilogue) == 136
-    assert [f[0] for f in GemmEpilogue._fields_] == ["bias", "rank_u", "rank_v", "aux_bf16", "residual_f32", "out_pre_bf16", "out_bf16",
-                                                     "out_f32", "act", "ld_rank_u", "ld_aux", "ld_res", "ld_pre", "ld_out_bf16",
-                                                     "ld_out_f32", "split_k", "drop_seed", "drop_thr16", "drop_scale", "drop_ld", "row_sums", "row_stats", "col_sum_w"]
+    # field names, their order and each field's type, as the headers declare them
+    assert GemmEpilogue._fields_ == HR.struct_fields(HEADER, "clibd_gemm_epilogue") and len(GemmEpilogue._fields_) == 23
+    assert OptimGroup._fields_ == HR.struct_fields(ROOT / "include" / "clibd_hip_optim.h", "clibd_optim_group") and ctypes.sizeof(OptimGroup) == 16
 
 
 def test_host_side_validation_needs_no_gpu(lib):
@@ -192,7 +244,6 @@ def test_hot_kernels_use_no_scratch():
     units compile in parallel (~75 s).  Allowed: the six attention instantiations whose 2-10 spilled registers were measured faster than their
     spill-free alternatives (profiles/r06_exp_attention_spills.log), none of them on the metric's path."""
     import concurrent.futures as cf
-    import subprocess
 
     from clibd_amd import build
 
@@ -201,24 +252,9 @@ def test_hot_kernels_use_no_scratch():
         "attention_bwd_kernelILi10ELb0ELb0ELb1ELi4ELi160E": 28, "attention_bwd_kernelILi10ELb0ELb0ELb0ELi4ELi160E": 28, "attention_bwd_kernelILi16ELb1ELb0ELb1ELi4ELi256E": 44,
     }
 
-    def report(unit):
-        r = subprocess.run([build._hipcc(), f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "-Wno-unused-value", "--cuda-device-only", "-c",
-                            str(build.CSRC / f"{unit}.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
-        assert r.returncode == 0, r.stderr[-2000:]
-        out, name = [], None
-        for line in r.stderr.splitlines():
-            m = re.search(r"remark:\s+(Function Name|ScratchSize \[bytes/lane\]):\s*(\S+)", line)
-            if not m:
-                continue
-            if m.group(1) == "Function Name":
-                name = m.group(2)
-            elif name:
-                out.append((name, int(m.group(2))))
-        return out
-
     units = ["gemm256", "attention", "layernorm", "lora", "gemm", "gemm256_tn", "loss"]
     with cf.ThreadPoolExecutor(max_workers=4) as ex:
-        rows = [r for res in ex.map(report, units) for r in res]
+        rows = [(k["name"], k["scratch"]) for res in ex.map(build.resource_usage, units) for k in res]
     assert sum(1 for n, _ in rows if "gemm256" in n) >= 40 and len(rows) >= 120, len(rows)
     bad = []
     for name, scratch in rows:

