@@ -526,7 +526,8 @@ extern "C" int clibd_lora_wgrad(const void* dqkv, int ld_dqkv, const void* x_bf1
     // large M: the MFMA form (needs whole 32-token slabs, 128-column segments and the dt rows at 16-byte pitch); round 6: with a partials
     // workspace ANY whole-slab M takes it (its sums are fixed-order; the VALU kernel below ends in float atomics), so that a step at the
     // small batches of the parity / fidelity tests (32 x 197 = 6 304 rows) is as bit-reproducible as one at the metric's batch
-    if (M % LWM_ROWS == 0 && (M >= 8192 || workspace != nullptr) && H % 128 == 0 && (H / 128 == 3 || H / 128 == 4 || H / 128 == 6 || H / 128 == 8) && ld_dt % 8 == 0) {
+    // (every H / 128 in 1 .. 8 has its instantiation: clibd_lora_workspace_bytes promises the fixed-order form for all of them)
+    if (M % LWM_ROWS == 0 && (M >= 8192 || workspace != nullptr) && H % 128 == 0 && ld_dt % 8 == 0) {
         const int num_cus = lora_num_cus();
         const int tiles = H / 128;
         const int want = (2 * num_cus + 5) / 6;   // x 6 segments: two workgroups (2 x 56 KiB of LDS at H = 768) per CU
@@ -546,9 +547,13 @@ extern "C" int clibd_lora_wgrad(const void* dqkv, int ld_dqkv, const void* x_bf1
                            (const unsigned short*)dqkv, ld_dqkv, (const unsigned short*)x_bf16, (const unsigned short*)t_bf16, \
                            (const unsigned short*)dt_bf16, ld_dt, M, H, dA_q, dA_v, dB_q, dB_v, 0, ws);               \
     } while (0)
-        if (tiles == 3) LWM_LAUNCH(3);
+        if (tiles == 1) LWM_LAUNCH(1);
+        else if (tiles == 2) LWM_LAUNCH(2);
+        else if (tiles == 3) LWM_LAUNCH(3);
         else if (tiles == 4) LWM_LAUNCH(4);
+        else if (tiles == 5) LWM_LAUNCH(5);
         else if (tiles == 6) LWM_LAUNCH(6);
+        else if (tiles == 7) LWM_LAUNCH(7);
         else LWM_LAUNCH(8);
 #undef LWM_LAUNCH
         if (int e = check_launch("lora_wgrad")) return e;

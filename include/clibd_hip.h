@@ -284,8 +284,10 @@ int clibd_lora_pack(const float* a_q, const float* a_v, const float* b_q, const 
  * carry ranks 5..8 in a second slot whose t comes from here).  x bf16 row stride ld_x (% 8), H % 8 == 0. */
 int clibd_lora_down_proj(const void* x_bf16, int ld_x, const void* a_cat_bf16, int M, int H, void* t_bf16, void* stream);
 /* workspace (ABI 3; may be NULL): clibd_lora_workspace_bytes(M, H) bytes, 16-byte aligned.  With it the MFMA forms (M % 32 == 0,
- * H % 128 == 0) write per-workgroup partials there and a last kernel adds them in a fixed order: no contended float atomics (38-54 us
- * of a 286-377 us backward at M = 403 456 / 272 384) and gradients that are bit-reproducible run to run; NULL keeps the float atomics. */
+ * H % 128 == 0: every H = 128, 256, ..., 1024 qualifies, and clibd_lora_workspace_bytes is non-zero exactly for these shapes) write
+ * per-workgroup partials there and a last kernel adds them in a fixed order: no contended float atomics (38-54 us
+ * of a 286-377 us backward at M = 403 456 / 272 384) and gradients that are bit-reproducible run to run; NULL keeps the float atomics.
+ * Every other shape (ragged M, H % 128 == 64) takes the VALU kernel and its float atomics whether or not a workspace is passed. */
 size_t clibd_lora_workspace_bytes(int M, int H);
 int clibd_lora_wgrad(const void* dqkv, int ld_dqkv, const void* x_bf16, const void* t_bf16, const void* dt_bf16,
                      int ld_dt, int M, int H, float* dA_q, float* dA_v, float* dB_q, float* dB_v,
